@@ -2,16 +2,24 @@
 """Training-throughput benchmark of the MI355X hot path (BASELINE.json `metric`: training clips/sec
 for EnvNet-v2 & AST).
 
-Default invocation (what the driver runs) times BOTH configs on the same GPUs, one after the other:
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline figure needs: it
+builds configs[1] (EnvNet-v2), warms up, times the K steps and prints the result line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` also writes what the last timed
+step computed (dump_leg below) as DIR/<name>.npy, so that two builds can be compared output for output: with
+the same arguments the inputs are identical from run to run.
+
+`--full` adds everything else this benchmark measures: the HBM / MFMA calibrations of the box, the live
+per-kernel probes with their rooflines, the AST legs and the CPU baselines.  It times ALL configs on the same
+GPUs, one after the other:
   * configs[1] — EnvNet-v2, bf16 compute (f32 master params / grads / Adam state), batch 256 per GPU:
     on-GPU BC mixing -> forward -> soft-label loss -> backward -> (N>1: RCCL gradient all-reduce)
     -> global-norm clip 1.0 -> Adam(lr 1e-4, wd 1e-4).  This is the top-level JSON line.
   * configs[2] — AST, bf16, batch 256 per GPU: on-GPU log-mel -> SpecAugment + Mixup -> forward ->
     soft-label loss -> backward -> (all-reduce) -> clip + Adam.  Nested as the "ast" object with its
     own value / ms_per_step / roofline (attention forward, the north-star MFMA kernel) / cpu_baseline.
-Synthetic 5 s @ 44.1 kHz clips resident in HBM.  `--model envnet|ast` times one leg only (profiling).
+Synthetic 5 s @ 44.1 kHz clips resident in HBM.  `--model envnet|ast|ast-fp8` times one leg only (profiling).
 
-python bench.py [--gpus N --steps K --warmup W].  N > 1 runs one process per GPU: under a launcher
+python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  N > 1 runs one process per GPU: under a launcher
 (torch.distributed.run: RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in the env) WORLD_SIZE must equal N;
 without one, this process starts ``torch.distributed.run --nproc-per-node N`` itself (before it
 touches the GPU) and exits with its status.  Every rank checks dist.get_world_size() == N.  Rank 0
@@ -55,18 +63,24 @@ def log(msg):
     print(f"[bench {time.time() - T_START:7.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one per GPU); default: WORLD_SIZE under a launcher, else 1")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--model", choices=["both", "envnet", "ast", "ast-fp8"], default="both",
-                    help="both = EnvNet-v2 leg + AST bf16 leg + AST fp8-mixed leg (config 5's linears)")
+    ap.add_argument("--model", choices=["both", "envnet", "ast", "ast-fp8"], default=None,
+                    help="both = EnvNet-v2 leg + AST bf16 leg + AST fp8-mixed leg (config 5's linears); "
+                         "default: envnet, with --full both")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline leg: box calibrations, live per-kernel probes + rooflines, the AST "
+                         "legs and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of each leg computed as DIR/<name>.npy (float32)")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU EnvNet batch (default 256)")
     ap.add_argument("--ast-batch", type=int, default=None, help="per-GPU AST batch (default 256)")
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--probe", default=None, help="comma list of probe tags to time live (default: auto)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="nccl (= RCCL, the product path); gloo only to rehearse N > 1 ranks on one GPU")
@@ -74,7 +88,12 @@ def parse():
                     help="N > 1, EnvNet FC1 weight gradient: all-gather the bf16 operands and defer the averaged "
                          "gradient to the fused Adam GEMM (the N = 1 program), the same with each rank updating "
                          "its row slice only, or materialise + chunked all-reduce")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.model is None:
+        args.model = "both" if args.full else "envnet"
+    return args
 
 
 def free_port() -> int:
@@ -147,9 +166,11 @@ def build_envnet_step(args, dev, rank, world, B):
             ddp.finish()
         opt.step()
         opt.zero_grad(set_to_none=True)
+        step.outputs = z.detach()
         return loss
 
     step.ddp = ddp
+    step.model = model
     tags = ["t0b.fwd", "t0b.dgrad", "t0b.wgrad", "conv1.fwd", "conv1.wgrad", "conv2.fwd", "conv2.dgrad",
             "conv2.wgrad", "fc1.fwd", "fc1.wgrad", "fc1.dgrad", "optim.step", "frontend.fwd", "frontend.bwd"]
     workload = "EnvNet-v2 train step (BC-mix, fwd, soft-CE, bwd, clip, Adam), ESC-50 shape"
@@ -388,7 +409,7 @@ def leg_result(model, B, world, steps, warmup, elapsed, loss, kstats, flop_per_c
         out["comm"] = comm
     if model == "envnet":
         out["frontend_path"] = frontend_summary(regions, B)
-    if model.startswith("ast"):
+    if model.startswith("ast") and (args.full or ks):
         out["attention"] = attention_summary(model, ks, peak_tf)
     if out["dominant_kernel"] is None:
         out.pop("dominant_kernel")
@@ -563,6 +584,40 @@ def add_box_fraction(leg: dict, box_gbs: float, box_tf: float = None):
         fp["frac_vs_box"] = round(fp["achieved_gbs"] / box_gbs, 4)
 
 
+DUMP_PARAM_SAMPLE = 1 << 20  # elements kept of each parameter larger than this
+DUMP_LEG_BYTES = 20 << 20    # float32 bytes per leg: three legs stay under 64 MB
+
+
+def dump_leg(out_dir, leg: str, step, loss: float) -> dict:
+    """What the leg's last timed step handed its caller, as float32 <out_dir>/<leg>_<name>.npy: the loss, the
+    model outputs of that step's batch (EnvNet logits / AST probabilities) and the parameters after its Adam
+    update.  A parameter of more than DUMP_PARAM_SAMPLE elements is written as a fixed sample (sorted indices
+    from numpy's default_rng seeded with the parameter's position), so the files of one leg stay below
+    DUMP_LEG_BYTES; the same arguments give the same indices in every run and build."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"loss": np.asarray([loss], dtype=np.float32),
+              "outputs": step.outputs.float().cpu().numpy()}
+    chunks = []
+    for i, p in enumerate(step.model.parameters()):
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            idx = np.sort(np.random.default_rng(i).integers(0, flat.numel(), DUMP_PARAM_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        chunks.append(flat.float().cpu().numpy())
+    arrays["params"] = np.concatenate(chunks)
+    budget = (DUMP_LEG_BYTES - arrays["outputs"].nbytes - 4) // 4
+    if arrays["params"].size > budget:  # many large parameters: an even stride over the per-parameter samples
+        arrays["params"] = arrays["params"][np.linspace(0, arrays["params"].size - 1, budget).astype(np.int64)]
+    written = {}
+    for name, a in arrays.items():
+        assert a.dtype == np.float32
+        np.save(out_dir / f"{leg}_{name}.npy", a)
+        written[f"{leg}_{name}"] = list(a.shape)
+    return written
+
+
 def free_leg():
     from src.miaudio import kernels as K
     K._WS.clear()
@@ -579,17 +634,29 @@ def main():
     check_world(args.gpus, dist.get_world_size() if world > 1 else 1)
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
-    calib = hbm_calibration(dev)
-    log(f"HBM calibration: {calib['gbs']} GB/s streaming copy on this box")
-    mcal = mfma_calibration(dev)
-    log(f"MFMA calibration: {mcal['tflops']} TFLOP/s bf16 on this box")
-    results = {}
+    calib = mcal = None
+    if args.full:
+        calib = hbm_calibration(dev)
+        log(f"HBM calibration: {calib['gbs']} GB/s streaming copy on this box")
+        mcal = mfma_calibration(dev)
+        log(f"MFMA calibration: {mcal['tflops']} TFLOP/s bf16 on this box")
+    results, dumped = {}, {}
+
+    def probe_tags(tags):  # live per-kernel events ride in the timed steps: --full (or an explicit --probe) only
+        return args.probe.split(",") if args.probe else (tags if args.full else [])
+
+    def dump(leg, step, loss):
+        if args.dump_outputs and rank == 0:
+            dumped.update(dump_leg(args.dump_outputs, leg, step, loss))
+            log(f"{leg}: outputs of the last timed step written to {args.dump_outputs}")
+
     if args.model in ("both", "envnet"):
         log("EnvNet-v2 leg: building")
         B = args.batch or 256
         step, fpc, tags, workload = build_envnet_step(args, dev, rank, world, B)
-        tags = args.probe.split(",") if args.probe else tags
+        tags = probe_tags(tags)
         el, loss, ks = time_leg(step, tags, args, world, dev, args.warmup, args.steps)
+        dump("envnet", step, loss)
         results["envnet"] = leg_result("envnet", B, world, args.steps, args.warmup, el, loss, ks, fpc, args,
                                        workload)
         results["envnet"]["config"]["model"] = "envnet_v2"
@@ -602,8 +669,9 @@ def main():
         log("AST leg: building")
         B = args.ast_batch or 256  # AST at batch 256 on one MI355X
         step, fpc, tags, workload = build_ast_step(args, dev, rank, world, B)
-        tags = args.probe.split(",") if args.probe else tags
+        tags = probe_tags(tags)
         el, loss, ks = time_leg(step, tags, args, world, dev, args.warmup, args.steps)
+        dump("ast", step, loss)
         results["ast"] = leg_result("ast", B, world, args.steps, args.warmup, el, loss, ks, fpc, args, workload,
                                     roof_tag="attn.fwd")
         results["ast"]["config"]["model"] = "ast"
@@ -616,8 +684,9 @@ def main():
         log("AST fp8-mixed leg: building")
         B = args.ast_batch or 256
         step, fpc, tags, workload = build_ast_step(args, dev, rank, world, B, compute="fp8")
-        tags = args.probe.split(",") if args.probe else tags
+        tags = probe_tags(tags)
         el, loss, ks = time_leg(step, tags, args, world, dev, args.warmup, args.steps)
+        dump("ast_fp8", step, loss)
         results["ast_fp8"] = leg_result("ast_fp8", B, world, args.steps, args.warmup, el, loss, ks, fpc, args,
                                         workload, roof_tag="attn.fwd")
         results["ast_fp8"]["config"]["model"] = "ast"
@@ -629,17 +698,21 @@ def main():
     if "ast" in results or "ast_fp8" in results:
         from src.miaudio import kernels as K
         K.check_attention_errors()  # raises if a timed step's one-pass attention backward gave up a dQ hand-off
-    for leg in results.values():
-        add_box_fraction(leg, calib["gbs"], mcal["tflops"])
+    if args.full:
+        for leg in results.values():
+            add_box_fraction(leg, calib["gbs"], mcal["tflops"])
     out = results.get("envnet") or results.get("ast") or results["ast_fp8"]
     if "envnet" in results and "ast" in results:
         out = dict(results["envnet"])
         out["ast"] = results["ast"]
     if "ast_fp8" in results and out is not results["ast_fp8"]:
         out["ast_fp8"] = results["ast_fp8"]
-    out["hbm_calibration"] = calib
-    out["mfma_calibration"] = mcal
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        out["hbm_calibration"] = calib
+        out["mfma_calibration"] = mcal
+    if dumped:
+        out["dumped_outputs"] = dumped
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         threads, why = cpu_threads()
         log(f"CPU baseline threads: {threads} ({why})")
         if "envnet" in results:

@@ -51,6 +51,42 @@ def test_check_world():
         bench.check_world(8, 1)
 
 
+def test_plain_run_is_the_headline_leg_alone_and_full_adds_the_rest():
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (plain.full, plain.model, plain.steps, plain.warmup, plain.dump_outputs) == (False, "envnet", 7, 2, None)
+    full = bench.parse(["--gpus", "1", "--full", "--dump-outputs", "d"])
+    assert (full.full, full.model, full.dump_outputs) == (True, "both", "d")
+    assert bench.parse(["--full", "--model", "ast"]).model == "ast" and bench.parse(["--model", "ast"]).model == "ast"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_leg_writes_float32_arrays_with_fixed_samples(tmp_path, monkeypatch):
+    """--dump-outputs: loss, the last step's model outputs and the parameters, float32; a large parameter is a
+    fixed sample (same indices in every run) and one leg's files stay below its share of the 64 MB."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 100)
+    monkeypatch.setattr(bench, "DUMP_LEG_BYTES", 4 * (6 + 1 + 150))
+
+    def step():
+        pass
+    step.model = torch.nn.ParameterList([torch.nn.Parameter(torch.arange(1000.0)),
+                                         torch.nn.Parameter(torch.arange(50.0).to(torch.bfloat16))])
+    step.outputs = torch.arange(6.0).reshape(2, 3).to(torch.bfloat16)
+    shapes = bench.dump_leg(tmp_path / "a", "envnet", step, 1.5)
+    assert shapes == {"envnet_loss": [1], "envnet_outputs": [2, 3], "envnet_params": [150]}
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in shapes}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["envnet_loss"][0] == 1.5 and np.array_equal(got["envnet_outputs"], np.arange(6.0).reshape(2, 3))
+    big, small = got["envnet_params"][:100], got["envnet_params"][100:]
+    assert np.array_equal(small, np.arange(50.0)) and np.all(np.diff(big) >= 0) and len(set(big)) > 50
+    bench.dump_leg(tmp_path / "b", "envnet", step, 1.5)
+    assert np.array_equal(np.load(tmp_path / "b" / "envnet_params.npy"), got["envnet_params"])
+    monkeypatch.setattr(bench, "DUMP_LEG_BYTES", 4 * (6 + 1 + 30))  # over the leg's budget: strided down to it
+    assert bench.dump_leg(tmp_path / "c", "envnet", step, 1.5)["envnet_params"] == [30]
+
+
 def test_attention_summary_credited_and_counter_figures():
     """The AST legs' attention object: credited rate from the probed launches (forward + backward FLOPs of
     SURVEY §8(d) over their live time) and the MFMA-busy figures of the committed SQ profile."""

@@ -4,7 +4,7 @@
 # runs bench.py with the product library, then with the given build of the same C ABI selected by
 # MIAUDIO_LIB (src/miaudio/lib.py) -- the product .so is never touched -- alternating twice; JSON lines
 # in gpurun_out/ab/.
-ARGS=${1:-"--model ast --steps 5 --warmup 2 --no-cpu-baseline"}
+ARGS=${1:-"--full --model ast --steps 5 --warmup 2 --no-cpu-baseline"}
 REF=$2
 OUT=gpurun_out/ab
 mkdir -p $OUT

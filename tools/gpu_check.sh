@@ -14,9 +14,9 @@ for s in $STAGES; do
     smoke)
       timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 ;;
     envnet)
-      timeout -k 10 300 python -u bench.py > $OUT/bench_envnet.log 2>&1 ;;
+      timeout -k 10 300 python -u bench.py --full > $OUT/bench_envnet.log 2>&1 ;;
     ast)
-      timeout -k 10 300 python -u bench.py --model ast --no-cpu-baseline > $OUT/bench_ast.log 2>&1 ;;
+      timeout -k 10 300 python -u bench.py --full --model ast --no-cpu-baseline > $OUT/bench_ast.log 2>&1 ;;
   esac
   echo "stage $s ok"
 done

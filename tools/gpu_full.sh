@@ -11,7 +11,7 @@ HB=$!
 trap "kill $HB 2>/dev/null" EXIT
 timeout -k 10 1500 python -u -m pytest tests -x -m gpu -v --timeout 600 --timeout-method thread > $OUT/gpu_tests.log 2>&1 &&
 timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 &&
-timeout -k 10 600 python -u bench.py ${2:-} > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python -u bench.py ${2:---full} > $OUT/bench.json 2> $OUT/bench.err
 rc=$?
 tail -3 $OUT/gpu_tests.log
 exit $rc

@@ -9,10 +9,10 @@ HB=$!
 trap "kill $HB 2>/dev/null" EXIT
 LEGS=${LEGS:-"envnet ast ast-fp8"}
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || exit $?
+  timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit $?
 fi
 for leg in $LEGS; do
-  bash tools/profile.sh $leg "--model $leg --steps 3 --warmup 2 --no-cpu-baseline" \
-      "--model $leg --steps 2 --warmup 1 --no-cpu-baseline" "trace fetch write sq" > $OUT/prof_$leg.log 2>&1 || exit $?
+  bash tools/profile.sh $leg "--full --model $leg --steps 3 --warmup 2 --no-cpu-baseline" \
+      "--full --model $leg --steps 2 --warmup 1 --no-cpu-baseline" "trace fetch write sq" > $OUT/prof_$leg.log 2>&1 || exit $?
 done
 echo "profile ok"

@@ -23,7 +23,7 @@ for s in $STAGES; do
       timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       rc=$? ;;
     bench)
-      timeout -k 10 500 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 500 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
       rc=$? ;;
     attnbwd)
       BATCH=${BATCH:-256} timeout -k 10 300 python -u tools/bench_attn_bwd.py > $OUT/attn_bwd.log 2>&1

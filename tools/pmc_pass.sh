@@ -2,7 +2,7 @@
 # One rocprofv3 PMC pass (counters only beside --kernel-trace) over a short bench run.
 #   bash tools/pmc_pass.sh <tag> "<counters>" "<bench args>" [kernel-regex]
 set -e
-TAG=$1; CTR=$2; ARGS=${3:-"--steps 2 --warmup 1 --no-cpu-baseline"}; RX=${4:-""}
+TAG=$1; CTR=$2; ARGS=${3:-"--full --steps 2 --warmup 1 --no-cpu-baseline"}; RX=${4:-""}
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT

@@ -6,8 +6,8 @@
 # Outputs under gpurun_out/prof_<tag>/ ; tools/pmc_summary.py condenses them into profiles/.
 set -e
 TAG=${1:-envnet}
-ARGS=${2:-"--steps 5 --warmup 2 --no-cpu-baseline"}
-PMC_ARGS=${3:-"--steps 2 --warmup 1 --no-cpu-baseline"}
+ARGS=${2:-"--full --steps 5 --warmup 2 --no-cpu-baseline"}
+PMC_ARGS=${3:-"--full --steps 2 --warmup 1 --no-cpu-baseline"}
 PASSES=${4:-"trace fetch write"}
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG

@@ -2,7 +2,7 @@
 # rocprofv3 kernel trace + stats of one bench configuration -> gpurun_out/prof_<tag>/trace
 set -e
 TAG=${1:-envnet}
-ARGS=${2:-"--steps 5 --warmup 2 --no-cpu-baseline"}
+ARGS=${2:-"--full --steps 5 --warmup 2 --no-cpu-baseline"}
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
