@@ -852,3 +852,95 @@ def gemm_mxfp8(a: MXTensor, b: MXTensor, E: L.MiaEpilogue, tag: str | None = Non
         e1.record()
         nb = (M + N) * K * (1 + 1 / 32) + M * N * (4 if E.dtype == L.F32 else 2)
         PROBE[tag].append((e0, e1, 2 * M * N * K, nb))
+
+
+# ---------------------------------------------------------------------------------------------- LEAF frontend
+def leaf_check_args(B: int, T: int, F: int, Kt: int, pool: int) -> None:
+    """The geometry mia_leaf_energy_* accept (checked here before anything is allocated or launched)."""
+    if not (3 <= Kt <= 1023 and Kt % 2 == 1):
+        raise ValueError(f"leaf: kernel_size {Kt} must be odd and in [3, 1023]")
+    if not (32 <= pool <= 1024 and pool % 32 == 0):
+        raise ValueError(f"leaf: pool {pool} must be a multiple of 32 in [32, 1024]")
+    if T < pool:
+        raise ValueError(f"leaf: T = {T} is shorter than one pool window ({pool})")
+    if not (1 <= F <= 65535 and 1 <= B <= 65535):
+        raise ValueError(f"leaf: B = {B}, F = {F} out of range")
+
+
+def _leaf_shapes(x: torch.Tensor, w: torch.Tensor, pool: int):
+    if x.ndim != 2 or w.ndim != 3 or w.shape[0] != 2:
+        raise ValueError(f"leaf: x must be [B][T] and w [2][F][Kt], got {tuple(x.shape)} and {tuple(w.shape)}")
+    B, T = x.shape
+    _, F, Kt = w.shape
+    leaf_check_args(B, T, F, Kt, pool)
+    if x.dtype != torch.float32 or w.dtype != torch.float32:
+        raise TypeError("leaf: x and w must be float32")
+    L.require_device(x, "leaf")
+    L.require_device(w, "leaf")
+    return B, T, F, Kt
+
+
+def leaf_energy_fwd(x: torch.Tensor, w: torch.Tensor, pool: int, compute: int, tag: str | None = None) -> torch.Tensor:
+    """P [B][F][T // pool] f32: pooled Gabor energy of x [B][T] under the bank w [2][F][Kt] (mia_leaf_energy_fwd)."""
+    B, T, F, Kt = _leaf_shapes(x, w, pool)
+    x, w = x.contiguous(), w.contiguous()
+    lib = L.load()
+    P = torch.empty(B, F, T // pool, dtype=torch.float32, device=x.device)
+    ws = workspace(lib.mia_leaf_workspace_bytes(B, T, F, Kt, pool, 0), x.device, "leaf") if compute == L.BF16 else None
+    with probe(tag or "", 4.0 * B * F * Kt * T, x.numel() * 4 + w.numel() * 4 + P.numel() * 4):
+        L.check(lib.mia_leaf_energy_fwd(x.data_ptr(), w.data_ptr(), P.data_ptr(), B, T, F, Kt, pool, compute,
+                                        L.ptr(ws), _s()), "mia_leaf_energy_fwd")
+    return P
+
+
+def leaf_energy_bwd(x: torch.Tensor, w: torch.Tensor, gP: torch.Tensor, pool: int, compute: int,
+                    tag: str | None = None) -> torch.Tensor:
+    """dw [2][F][Kt] f32 of sum(P * gP) (mia_leaf_energy_bwd; deterministic)."""
+    B, T, F, Kt = _leaf_shapes(x, w, pool)
+    if tuple(gP.shape) != (B, F, T // pool) or gP.dtype != torch.float32:
+        raise ValueError(f"leaf: gP must be f32 {(B, F, T // pool)}, got {tuple(gP.shape)} {gP.dtype}")
+    x, w, gP = x.contiguous(), w.contiguous(), gP.contiguous()
+    lib = L.load()
+    dw = torch.empty_like(w)
+    ws = workspace(lib.mia_leaf_workspace_bytes(B, T, F, Kt, pool, 1), x.device, "leaf")
+    with probe(tag or "", 8.0 * B * F * Kt * T, x.numel() * 4 + w.numel() * 8 + gP.numel() * 4):
+        L.check(lib.mia_leaf_energy_bwd(x.data_ptr(), w.data_ptr(), gP.data_ptr(), dw.data_ptr(), B, T, F, Kt, pool,
+                                        compute, ws.data_ptr(), _s()), "mia_leaf_energy_bwd")
+    return dw
+
+
+def _pcen_shapes(P: torch.Tensor, r: torch.Tensor, delta: torch.Tensor):
+    if P.ndim != 3 or P.dtype != torch.float32:
+        raise ValueError(f"pcen: P must be f32 [B][F][Tp], got {tuple(P.shape)} {P.dtype}")
+    B, F, Tp = P.shape
+    if tuple(r.shape) != (F,) or tuple(delta.shape) != (F,) or B < 1 or B > 65535 or Tp < 1:
+        raise ValueError(f"pcen: r / delta must be [{F}] and 1 <= B <= 65535, Tp >= 1")
+    L.require_device(P, "pcen")
+    return B, F, Tp
+
+
+def pcen_fwd(P: torch.Tensor, r: torch.Tensor, delta: torch.Tensor, eps: float, tag: str | None = None) -> torch.Tensor:
+    B, F, Tp = _pcen_shapes(P, r, delta)
+    P = P.contiguous()
+    y = torch.empty_like(P)
+    with probe(tag or "", 30.0 * P.numel(), P.numel() * 8):
+        L.check(L.load().mia_pcen_fwd(P.data_ptr(), r.contiguous().data_ptr(), delta.contiguous().data_ptr(), eps,
+                                      y.data_ptr(), B, F, Tp, _s()), "mia_pcen_fwd")
+    return y
+
+
+def pcen_bwd(P: torch.Tensor, r: torch.Tensor, delta: torch.Tensor, eps: float, gy: torch.Tensor,
+             tag: str | None = None):
+    """(gP, dr, ddelta) of y = pcen(P) under the upstream gradient gy (mia_pcen_bwd; deterministic)."""
+    B, F, Tp = _pcen_shapes(P, r, delta)
+    P, gy = P.contiguous(), gy.contiguous()
+    lib = L.load()
+    gP = torch.empty_like(P)
+    dr = torch.empty(F, dtype=torch.float32, device=P.device)
+    dd = torch.empty(F, dtype=torch.float32, device=P.device)
+    ws = workspace(lib.mia_pcen_workspace_bytes(B, F), P.device, "pcen")
+    with probe(tag or "", 150.0 * P.numel(), P.numel() * 12):
+        L.check(lib.mia_pcen_bwd(P.data_ptr(), r.contiguous().data_ptr(), delta.contiguous().data_ptr(), eps,
+                                 gy.data_ptr(), gP.data_ptr(), dr.data_ptr(), dd.data_ptr(), ws.data_ptr(), B, F, Tp,
+                                 _s()), "mia_pcen_bwd")
+    return gP, dr, dd

@@ -156,6 +156,12 @@ SIGNATURES = {
     "mia_bc_partner": (C.c_int, [vp, i32, vp, i32, vp, vp, vp]),
     "mia_stretch_gain": (C.c_int, [vp, i64, i32, vp, vp, vp, vp]),
     "mia_spec_augment_mixup":(C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "mia_leaf_workspace_bytes": (i64, [i32, i64, i32, i32, i32, i32]),
+    "mia_leaf_energy_fwd": (C.c_int, [vp, vp, vp, i32, i64, i32, i32, i32, i32, vp, vp]),
+    "mia_leaf_energy_bwd": (C.c_int, [vp, vp, vp, vp, i32, i64, i32, i32, i32, i32, vp, vp]),
+    "mia_pcen_workspace_bytes": (i64, [i32, i32]),
+    "mia_pcen_fwd": (C.c_int, [vp, vp, vp, f32, vp, i32, i32, i32, vp]),
+    "mia_pcen_bwd": (C.c_int, [vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "mia_last_error_string": (C.c_char_p, []),
     "mia_device_arch": (C.c_int, [C.c_char_p, i32]),
 }

@@ -650,6 +650,36 @@ int mia_stream_copy(const void* src, void* dst, int64_t bytes, mia_stream_t stre
 int64_t mia_mfma_rate_sink_floats(int32_t waves_per_simd);
 int mia_mfma_rate(float* sink, int32_t iters, int32_t waves_per_simd, mia_stream_t stream);
 
+/* LEAF frontend (leaf.py:7-50 GaborConv1d -> avg_pool1d(pool) -> PCEN; replaces two F.conv1d that write a
+ * [B][F][T] tensor each, the square-sum, F.avg_pool1d and the PCEN expression).
+ * x [B][T] f32; w [2][F][Kt] f32 (re, im rows of the Gabor bank, Kt odd in [3, 1023], h = Kt / 2);
+ * pool a multiple of 32 in [32, 1024]; T >= pool; Tp = T / pool (the T - Tp * pool tail feeds no output).
+ *   P[b][f][j] = mean over t in [j pool, (j + 1) pool) of (sum_k w[0][f][k] x[b][t + k - h])^2
+ *                                                        + (sum_k w[1][f][k] x[b][t + k - h])^2, x zero outside.
+ * compute MIA_BF16: x and w rounded to bf16, f32 accumulation, v_mfma_f32_32x32x16_bf16 with the Toeplitz
+ * operand formed in LDS; only P is written.  compute MIA_F32: f32 operands (parity path, plain FMA).
+ * mia_leaf_energy_bwd: dw [2][F][Kt] = d(sum P * gP) / dw (no gradient for x): the xr / xi of every frame are
+ * recomputed, scaled by (2 / pool) gP[b][f][t / pool] (rounded to bf16 in BF16 mode) and contracted over time
+ * against the same waveform; the contraction is split into f32 slabs in the workspace that are added in a
+ * fixed order (no atomics: bit-identical run to run).
+ * workspace: mia_leaf_workspace_bytes(.., backward) bytes, forward (backward = 0: the packed bf16 bank) or
+ * backward (backward = 1: the slabs); -1 for a geometry the kernels reject.  Any other geometry than the above
+ * returns an error and launches nothing. */
+int64_t mia_leaf_workspace_bytes(int32_t B, int64_t T, int32_t F, int32_t Kt, int32_t pool, int32_t backward);
+int mia_leaf_energy_fwd(const float* x, const float* w, float* P, int32_t B, int64_t T, int32_t F, int32_t Kt,
+                        int32_t pool, int32_t compute, void* workspace, mia_stream_t stream);
+int mia_leaf_energy_bwd(const float* x, const float* w, const float* gP, float* dw, int32_t B, int64_t T, int32_t F,
+                        int32_t Kt, int32_t pool, int32_t compute, void* workspace, mia_stream_t stream);
+/* PCEN as the reference computes it (leaf.py:46-50): M[j] = (P[j-2] + .. + P[j+2]) / 5 with zero padding (the
+ * divisor is 5 at the edges too), y = log(P / (eps + M)^r[f] + delta[f]); P, y, gy, gP [B][F][Tp] f32.
+ * mia_pcen_bwd: gP (the direct path and the one through M), dr [F], ddelta [F]; the per-filter sums go through
+ * mia_pcen_workspace_bytes(B, F) bytes of workspace in a fixed order. */
+int64_t mia_pcen_workspace_bytes(int32_t B, int32_t F);
+int mia_pcen_fwd(const float* P, const float* r, const float* delta, float eps, float* y, int32_t B, int32_t F,
+                 int32_t Tp, mia_stream_t stream);
+int mia_pcen_bwd(const float* P, const float* r, const float* delta, float eps, const float* gy, float* gP,
+                 float* dr, float* ddelta, void* workspace, int32_t B, int32_t F, int32_t Tp, mia_stream_t stream);
+
 const char* mia_last_error_string(void);
 int mia_device_arch(char* buf, int32_t len); /* gcnArchName of the current device */
 
