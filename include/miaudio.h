@@ -69,7 +69,9 @@ typedef struct MiaOperand {
  *   ADD_AUX  : v += aux[m][n]                       (residual connection into a new tensor)
  *   GELU_SAVE: aux[m][n] = v; v = gelu(v)          (MLP fc1: keeps the pre-activation for the backward)
  *   GELU_SAVE_D: aux[m][n] = gelu'(v); v = gelu(v) (MLP fc1: keeps the derivative the backward needs)
- *   DACT_MUL : v *= aux[m][n]                       (GELU backward from the saved derivative) */
+ *   DACT_MUL : v *= aux[m][n]                       (GELU backward from the saved derivative)
+ *   The 256x256 kernel rounds v to bf16 before the GELU_* / DACT_GELU / DACT_MUL of a bf16 output (as autocast
+ *   rounds a Linear's output) and rounds the result again; the other kernels apply them to the f32 v. */
 typedef struct MiaEpilogue {
   void* ptr;
   int32_t dtype, act, accumulate, aux_dtype;
