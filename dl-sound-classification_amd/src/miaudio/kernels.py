@@ -944,3 +944,115 @@ def pcen_bwd(P: torch.Tensor, r: torch.Tensor, delta: torch.Tensor, eps: float, 
                                  gy.data_ptr(), gP.data_ptr(), dr.data_ptr(), dd.data_ptr(), ws.data_ptr(), B, F, Tp,
                                  _s()), "mia_pcen_bwd")
     return gP, dr, dd
+
+
+# ------------------------------------------------------------------------------------ LEAF trunk glue
+def _lt_map(x: torch.Tensor, n: int, t: int, c: int, what: str):
+    if x.dtype not in (torch.float32, torch.bfloat16) or x.numel() != n * t * c or not x.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous f32 / bf16 ({n}, {t}, {c}) map, got {tuple(x.shape)} {x.dtype}")
+    if c % 8 or not 8 <= c <= 1024:
+        raise ValueError(f"{what}: c = {c} must be a multiple of 8 in [8, 1024]")
+    L.require_device(x, what)
+
+
+def _lt_ws(c: int, device) -> torch.Tensor:
+    return workspace(L.load().mia_lt_workspace_bytes(c), device, "leaftrunk")
+
+
+def lt_pool_stats(z: torch.Tensor, n: int, t: int, c: int, k: int, gamma: torch.Tensor, kshift, stats: bool = True,
+                  tag: str | None = None):
+    """One read of z (n, t, c): (win, argmax, partial, nblk) -- the raw winner (z's dtype) and u8 argmax of each of
+    the t // k windows, and (stats) the BN shifted sums of every frame about kshift for bn_finalize_shifted."""
+    _lt_map(z, n, t, c, "lt_pool_stats")
+    lib = L.load()
+    ot = t // k
+    win = torch.empty(n, ot, c, dtype=z.dtype, device=z.device)
+    am = torch.empty(n, ot, c, dtype=torch.uint8, device=z.device)
+    nblk = max(int(lib.mia_lt_stats_blocks(n, t, c, k)), 1)
+    part = torch.empty(nblk, c, 2, dtype=torch.float32, device=z.device) if stats else None
+    with probe(tag or "", 4.0 * z.numel(), z.numel() * z.element_size() + win.numel() * (z.element_size() + 1)):
+        L.check(lib.mia_lt_pool_stats(z.data_ptr(), L.dtype_code(z), n, t, c, k, gamma.data_ptr(), L.ptr(kshift),
+                                      win.data_ptr(), am.data_ptr(), L.ptr(part), nblk, _s()), "mia_lt_pool_stats")
+    return win, am, part, nblk
+
+
+def lt_pool_apply(win: torch.Tensor, n: int, ot: int, c: int, bn: BNState, out_dtype: torch.dtype, mean: bool = False,
+                  tag: str | None = None) -> torch.Tensor:
+    """relu(bn.scale * win + bn.shift): the pooled map (n, ot, c), or (mean) its time mean (n, c)."""
+    _lt_map(win, n, ot, c, "lt_pool_apply")
+    out = torch.empty((n, c) if mean else (n, ot, c), dtype=out_dtype, device=win.device)
+    with probe(tag or "", 3.0 * win.numel(), win.numel() * win.element_size() + out.numel() * out.element_size()):
+        L.check(L.load().mia_lt_pool_apply(win.data_ptr(), L.dtype_code(win), n, ot, c, bn.scale.data_ptr(),
+                                           bn.shift.data_ptr(), out.data_ptr(), L.dtype_code(out), int(mean), _s()),
+                "mia_lt_pool_apply")
+    return out
+
+
+def lt_pool_bwd_gather(dout: torch.Tensor, win: torch.Tensor, n: int, ot: int, c: int, bn: BNState, mean: bool = False,
+                       tag: str | None = None):
+    """(gm, dgamma, dbeta): gm f32 (n, ot, c) = dout * (bn.scale * win + bn.shift > 0); dout is (n, ot, c), or
+    (mean) the gradient dh (n, c) of the time-mean variant."""
+    _lt_map(win, n, ot, c, "lt_pool_bwd_gather")
+    if dout.numel() != (n * c if mean else n * ot * c) or not dout.is_contiguous():
+        raise ValueError(f"lt_pool_bwd_gather: dout has {dout.numel()} elements")
+    g = torch.empty(2, c, dtype=torch.float32, device=win.device)
+    gm = torch.empty(n, ot, c, dtype=torch.float32, device=win.device)
+    ws = _lt_ws(c, win.device)
+    with probe(tag or "", 6.0 * win.numel(), win.numel() * (win.element_size() + 4) + dout.numel() * dout.element_size()):
+        L.check(L.load().mia_lt_pool_bwd_gather(dout.data_ptr(), L.dtype_code(dout), int(mean), win.data_ptr(),
+                                                L.dtype_code(win), n, ot, c, bn.scale.data_ptr(), bn.shift.data_ptr(),
+                                                bn.mean.data_ptr(), bn.invstd.data_ptr(), gm.data_ptr(), g[0].data_ptr(),
+                                                g[1].data_ptr(), ws.data_ptr(), _s()), "mia_lt_pool_bwd_gather")
+    return gm, g[0], g[1]
+
+
+def lt_pool_bwd_apply(gm: torch.Tensor, argmax: torch.Tensor, z: torch.Tensor, n: int, t: int, c: int, k: int, gamma,
+                      bn: BNState, dgamma: torch.Tensor, dbeta: torch.Tensor, dbias: bool = True,
+                      tag: str | None = None):
+    """(dz, dbias): the BN backward of the pooled layer in one read of z and one write of dz (z's dtype)."""
+    _lt_map(z, n, t, c, "lt_pool_bwd_apply")
+    if gm.dtype != torch.float32 or gm.numel() != n * (t // k) * c or argmax.numel() != gm.numel():
+        raise ValueError("lt_pool_bwd_apply: gm / argmax must hold one entry per pooled cell and channel")
+    dz = torch.empty_like(z)
+    db = torch.empty(c, dtype=torch.float32, device=z.device) if dbias else None
+    ws = _lt_ws(c, z.device)
+    with probe(tag or "", 6.0 * z.numel(), 2 * z.numel() * z.element_size() + gm.numel() * 5):
+        L.check(L.load().mia_lt_pool_bwd_apply(gm.data_ptr(), argmax.data_ptr(), z.data_ptr(), L.dtype_code(z), n, t, c,
+                                               k, L.ptr(gamma), bn.mean.data_ptr(), bn.invstd.data_ptr(),
+                                               dgamma.data_ptr(), dbeta.data_ptr(), dz.data_ptr(), L.ptr(db),
+                                               ws.data_ptr(), _s()), "mia_lt_pool_bwd_apply")
+    return dz, db
+
+
+def lt_pcen_fwd(P: torch.Tensor, r: torch.Tensor, delta: torch.Tensor, eps: float, out_dtype: torch.dtype,
+                halo: int = 0, tag: str | None = None) -> torch.Tensor:
+    """Channels-last PCEN: P [B][F][Tp] f32 -> y (B, halo + Tp + halo, Fp), Fp = ceil(F / 8) * 8; pad channels and
+    halo rows are zero (mia_lt_pcen_fwd)."""
+    B, F, Tp = _pcen_shapes(P, r, delta)
+    P = P.contiguous()
+    Fp = (F + 7) // 8 * 8
+    y = torch.empty(B, Tp + 2 * halo, Fp, dtype=out_dtype, device=P.device)
+    with probe(tag or "", 30.0 * P.numel(), P.numel() * 4 + y.numel() * y.element_size()):
+        L.check(L.load().mia_lt_pcen_fwd(P.data_ptr(), r.contiguous().data_ptr(), delta.contiguous().data_ptr(), eps,
+                                         y.data_ptr(), L.dtype_code(y), B, F, Tp, halo, _s()), "mia_lt_pcen_fwd")
+    return y
+
+
+def lt_pcen_bwd(P: torch.Tensor, r: torch.Tensor, delta: torch.Tensor, eps: float, gy: torch.Tensor, halo: int = 0,
+                tag: str | None = None):
+    """(gP [B][F][Tp], dr, ddelta) from gy in lt_pcen_fwd's layout (mia_lt_pcen_bwd; deterministic)."""
+    B, F, Tp = _pcen_shapes(P, r, delta)
+    Fp = (F + 7) // 8 * 8
+    if tuple(gy.shape) != (B, Tp + 2 * halo, Fp) or not gy.is_contiguous():
+        raise ValueError(f"lt_pcen_bwd: gy must be contiguous {(B, Tp + 2 * halo, Fp)}, got {tuple(gy.shape)}")
+    P = P.contiguous()
+    lib = L.load()
+    gP = torch.empty_like(P)
+    dr = torch.empty(F, dtype=torch.float32, device=P.device)
+    dd = torch.empty(F, dtype=torch.float32, device=P.device)
+    ws = workspace(lib.mia_pcen_workspace_bytes(B, F), P.device, "pcen")
+    with probe(tag or "", 150.0 * P.numel(), P.numel() * 8 + gy.numel() * gy.element_size()):
+        L.check(lib.mia_lt_pcen_bwd(P.data_ptr(), r.contiguous().data_ptr(), delta.contiguous().data_ptr(), eps,
+                                    gy.data_ptr(), L.dtype_code(gy), gP.data_ptr(), dr.data_ptr(), dd.data_ptr(),
+                                    ws.data_ptr(), B, F, Tp, halo, _s()), "mia_lt_pcen_bwd")
+    return gP, dr, dd

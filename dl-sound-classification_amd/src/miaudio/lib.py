@@ -162,6 +162,14 @@ SIGNATURES = {
     "mia_pcen_workspace_bytes": (i64, [i32, i32]),
     "mia_pcen_fwd": (C.c_int, [vp, vp, vp, f32, vp, i32, i32, i32, vp]),
     "mia_pcen_bwd": (C.c_int, [vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mia_lt_stats_blocks": (i32, [i32, i32, i32, i32]),
+    "mia_lt_workspace_bytes": (i64, [i32]),
+    "mia_lt_pool_stats": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
+    "mia_lt_pool_apply": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]),
+    "mia_lt_pool_bwd_gather": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mia_lt_pool_bwd_apply": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mia_lt_pcen_fwd": (C.c_int, [vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, vp]),
+    "mia_lt_pcen_bwd": (C.c_int, [vp, vp, vp, f32, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "mia_last_error_string": (C.c_char_p, []),
     "mia_device_arch": (C.c_int, [C.c_char_p, i32]),
 }

@@ -682,6 +682,48 @@ int mia_pcen_fwd(const float* P, const float* r, const float* delta, float eps, 
 int mia_pcen_bwd(const float* P, const float* r, const float* delta, float eps, const float* gy, float* gP,
                  float* dr, float* ddelta, void* workspace, int32_t B, int32_t F, int32_t Tp, mia_stream_t stream);
 
+/* LEAF trunk glue (leaf.py:60-77 Conv1d -> BatchNorm1d -> ReLU -> MaxPool1d, three times, then
+ * AdaptiveAvgPool1d(1); replaces the BatchNorm statistics pass, the BN-apply + ReLU + MaxPool1d pass, their autograd
+ * and the transposes around them).  Maps are channels-last (n, t, c), MIA_F32 or MIA_BF16, c % 8 == 0 in [8, 1024]
+ * (c / 8 need not divide the block size: 384 works), 16-byte aligned; window k == stride in [1, 255], floor mode,
+ * ot = t / k.  No atomics: every sum runs in a fixed order.
+ * mia_lt_pool_stats: one read of z -> win (n, ot, c) (z's dtype, the raw winner of each window: max for gamma > 0,
+ *   min for gamma < 0, first position for gamma == 0, first occurrence on ties), argmax u8 (n, ot, c), and (partial
+ *   != NULL) the shifted sums about kshift[c] (NULL: 0) of EVERY frame, the t % k frames past the last window
+ *   included: partial[nblocks][c][2] f32 for mia_bn_finalize_shifted, nblocks = mia_lt_stats_blocks(n, t, c, k).
+ *   partial == NULL (eval mode): winners only.
+ * mia_lt_pool_apply: out = relu(scale * win + shift), (n, ot, c) in out_dtype; mean != 0: its mean over the ot
+ *   frames instead, out (n, c) in out_dtype (the pooled map is not written).
+ * mia_lt_pool_bwd_gather: gm f32 (n, ot, c) = dout * (scale * win + shift > 0), dgamma = sum gm * xhat(win),
+ *   dbeta = sum gm; dout (n, ot, c), or with mean_mode != 0 dh (n, c) standing for dh / ot on every frame.
+ * mia_lt_pool_bwd_apply: one read of z, one write of dz = gamma invstd (g - dbeta / P - xhat dgamma / P), P = n t,
+ *   g = gm at the argmax frame and 0 elsewhere; optional dbias[c] = sum over rows of dz.
+ * workspace: mia_lt_workspace_bytes(c) bytes.
+ * mia_lt_pcen_fwd / _bwd: mia_pcen_fwd / mia_pcen_bwd with y / gy channels-last: y (B, halo + Tp + halo, Fp) in
+ *   dtype, Fp = ceil(F / 8) * 8, channels >= F and the 2 * halo rows (halo <= 8) of every clip written as zero; the
+ *   transpose goes through LDS tiles.  F <= 1024.  MIA_F32: the same bits as mia_pcen_fwd / mia_pcen_bwd (gP, dr,
+ *   ddelta) on the transposed tensor.  workspace (bwd): mia_pcen_workspace_bytes(B, F) bytes. */
+int32_t mia_lt_stats_blocks(int32_t n, int32_t t, int32_t c, int32_t k);
+int64_t mia_lt_workspace_bytes(int32_t c);
+int mia_lt_pool_stats(const void* z, int32_t dtype, int32_t n, int32_t t, int32_t c, int32_t k, const float* gamma,
+                      const float* kshift, void* win, uint8_t* argmax, float* partial, int32_t nblocks,
+                      mia_stream_t stream);
+int mia_lt_pool_apply(const void* win, int32_t dtype, int32_t n, int32_t ot, int32_t c, const float* scale,
+                      const float* shift, void* out, int32_t out_dtype, int32_t mean, mia_stream_t stream);
+int mia_lt_pool_bwd_gather(const void* dout, int32_t dout_dtype, int32_t mean_mode, const void* win, int32_t dtype,
+                           int32_t n, int32_t ot, int32_t c, const float* scale, const float* shift, const float* mean,
+                           const float* invstd, float* gm, float* dgamma, float* dbeta, void* workspace,
+                           mia_stream_t stream);
+int mia_lt_pool_bwd_apply(const float* gm, const uint8_t* argmax, const void* z, int32_t dtype, int32_t n, int32_t t,
+                          int32_t c, int32_t k, const float* gamma, const float* mean, const float* invstd,
+                          const float* dgamma, const float* dbeta, void* dz, float* dbias, void* workspace,
+                          mia_stream_t stream);
+int mia_lt_pcen_fwd(const float* P, const float* r, const float* delta, float eps, void* y, int32_t dtype, int32_t B,
+                    int32_t F, int32_t Tp, int32_t halo, mia_stream_t stream);
+int mia_lt_pcen_bwd(const float* P, const float* r, const float* delta, float eps, const void* gy, int32_t dtype,
+                    float* gP, float* dr, float* ddelta, void* workspace, int32_t B, int32_t F, int32_t Tp,
+                    int32_t halo, mia_stream_t stream);
+
 const char* mia_last_error_string(void);
 int mia_device_arch(char* buf, int32_t len); /* gcnArchName of the current device */
 
