@@ -1,5 +1,6 @@
-// Shared pieces of the GEMM kernels (gemm.hip and its callers): the epilogue descriptor and its
-// vectorised store path, and the dense bf16 GEMM argument block.
+// Shared pieces of the GEMM kernels (the mia_gemm dispatcher gemm.hip and the kernel families it launches): the
+// epilogue descriptor and its vectorised store path, the dense bf16 GEMM argument block, and each family's
+// eligibility predicate and launcher.
 #pragma once
 #include "common.h"
 
@@ -204,28 +205,48 @@ static __device__ __forceinline__ void epi_store16(const EpiDev& e, int64_t m, i
 }
 
 
-// Rolling-window weight gradient of the 8x8, 32 -> 32 channel valid conv with a BN+ReLU pre-op
-// (wgrad8.hip): bf16 NHWC x (n, oh+7, ow+7, 32) raw, dy (n, oh, ow, 32); writes nblk f32 slabs
-// ws[nblk][32][2048] (OHWI columns) for the split-K reducer.
-struct W8Args {
-  const bf16* x;
-  const bf16* dy;
-  const float* ps;
-  const float* pt;
-  int n, h, w, oh, ow;
-  int nblk;
-  float* ws;
-};
-hipError_t wgrad8_launch(const W8Args& a, hipStream_t s);
+// -------------------------------------------------------------------------- host side
+// Shared by the kernel families: the device form of an epilogue, and the reduction of `split` f32 slabs
+// ws[split][M][N] through the epilogue e (gemm.hip).
+EpiDev to_dev(const MiaEpilogue& e);
+void launch_splitk_reduce(const float* ws, int split, int64_t M, int64_t N, const EpiDev& e, hipStream_t s);
 
-// 256 x 256 dense bf16 GEMM of the AST linears (mgemm.hip): eligibility, workspace, launch
+// The kernel families of mia_gemm, each in its own file: *_ok says whether the family takes a GEMM (asked only
+// by the selector in gemm.hip), *_run fills the family's argument block, picks the template instance, launches
+// it and reduces its split-K slabs where it has any.  `split` is >= 1 and the workspace holds `split` slabs.
+//   path 0, implicit-GEMM tile kernel (igemm.hip): takes everything
+int igemm_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64_t M, int64_t N, int64_t K,
+              int compute, int split, void* workspace, hipStream_t s);
+//   paths 1 and 2, row-window conv and its weight gradient (rowconv.hip)
+bool rowconv_ok(const MiaOperand& A, const MiaOperand& B, int64_t M, int64_t N, int64_t K, int compute, int split);
+int rowconv_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64_t M, int64_t N, hipStream_t s);
+bool rowwgrad_ok(const MiaOperand& A, const MiaOperand& B, int64_t M, int64_t N, int64_t K, int compute, int split);
+int rowwgrad_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64_t M, int64_t N, int split,
+                 void* workspace, hipStream_t s);
+//   the rolling-window case of path 2: 8x8, 32 -> 32 channel valid conv with a BN+ReLU pre-op (wgrad8.hip);
+//   wgrad8_ok presumes rowwgrad_ok
+bool wgrad8_ok(const MiaOperand& A, const MiaOperand& B, int64_t M);
+int wgrad8_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64_t M, int64_t N, int split,
+               void* workspace, hipStream_t s);
+//   paths 3 and 4, single-channel tap weight gradient and tap conv (tapconv.hip)
+bool tapwgrad_ok(const MiaOperand& A, const MiaOperand& B, int64_t M, int64_t N, int64_t K, int compute, int split);
+int tapwgrad_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64_t M, int64_t N, int split,
+                 void* workspace, hipStream_t s);
+bool tapconv_ok(const MiaOperand& A, const MiaOperand& B, int64_t M, int64_t N, int64_t K, int compute, int split);
+int tapconv_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, hipStream_t s);
+//   path 5, dense bf16 GEMM, 128 x 128 tiles (dgemm.hip); tile_sqsum_run fills MiaEpilogue.sqsum from a stored
+//   f32 output when the kernel that produced it did not
+bool dgemm_ok(const MiaOperand& A, const MiaOperand& B, int64_t M, int64_t N, int64_t K, int compute);
+int dgemm_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64_t M, int64_t N, int64_t K,
+              int split, void* workspace, hipStream_t s);
+int tile_sqsum_run(const float* c, int64_t ldc, int64_t M, int64_t N, double* sqsum, hipStream_t s);
+//   path 7, dense bf16 GEMM, 256 x 256 tiles, of the AST linears (mgemm.hip): with its own split and workspace
 bool mg_ok(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64_t M, int64_t N, int64_t K,
            int compute);
 int mg_split(int64_t M, int64_t N, int64_t K);
 int64_t mg_workspace_bytes(int64_t M, int64_t N, int64_t K, int colsum, int a_colsum = 0);
 int mg_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64_t M, int64_t N, int64_t K,
            void* workspace, hipStream_t s);
-
 
 
 }  // namespace mgemm

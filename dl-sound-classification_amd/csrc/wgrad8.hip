@@ -15,6 +15,19 @@
 #include "gemm_common.h"
 
 namespace mgemm {
+
+// bf16 NHWC x (n, oh+7, ow+7, 32) raw, dy (n, oh, ow, 32); writes nblk f32 slabs ws[nblk][32][2048] (OHWI
+// columns) for the split-K reducer.
+struct W8Args {
+  const bf16* x;
+  const bf16* dy;
+  const float* ps;
+  const float* pt;
+  int n, h, w, oh, ow;
+  int nblk;
+  float* ws;
+};
+
 namespace {
 
 constexpr int W8_NT = 512;
@@ -149,9 +162,29 @@ __global__ __launch_bounds__(W8_NT) void wgrad8_kernel(W8Args g) {
 
 }  // namespace
 
-hipError_t wgrad8_launch(const W8Args& a, hipStream_t s) {
-  wgrad8_kernel<<<a.nblk, W8_NT, 0, s>>>(a);
-  return hipGetLastError();
+// Among the GEMMs the row-window weight gradient takes (rowwgrad_ok): the trunk conv4 shape this kernel is for
+bool wgrad8_ok(const MiaOperand& A, const MiaOperand& B, int64_t M) {
+  return A.dtype == MIA_BF16 && M == 32 && B.c == 32 && B.kh == 8 && B.kw == 8 && B.sw == 1 && B.ph == 0 &&
+         B.pw == 0 && B.pre == MIA_PRE_AFFINE_RELU && B.h == B.oh + 7 && B.w == B.ow + 7;
+}
+
+// rolling 8-row window per (clip, column chunk), one slab per block
+int wgrad8_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64_t M, int64_t N, int split,
+               void* workspace, hipStream_t s) {
+  W8Args w8;
+  w8.x = reinterpret_cast<const bf16*>(B.ptr);
+  w8.dy = reinterpret_cast<const bf16*>(A.ptr);
+  w8.ps = B.pre_scale; w8.pt = B.pre_shift;
+  w8.n = B.n; w8.h = B.h; w8.w = B.w; w8.oh = B.oh; w8.ow = B.ow;
+  const int64_t items = (int64_t)B.n * cdiv(B.ow, 128);
+  w8.nblk = (int)std::min<int64_t>(std::min<int64_t>(split, 256), items);
+  w8.ws = reinterpret_cast<float*>(workspace);
+  wgrad8_kernel<<<w8.nblk, W8_NT, 0, s>>>(w8);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return mia::fail(-(int)err, "wgrad8 launch: %s", hipGetErrorString(err));
+  launch_splitk_reduce(w8.ws, w8.nblk, M, N, to_dev(E), s);
+  MIA_LAUNCH_CHECK("splitk_reduce");
+  return 0;
 }
 
 }  // namespace mgemm
