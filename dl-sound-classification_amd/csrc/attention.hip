@@ -99,14 +99,31 @@ __device__ __forceinline__ void fwd_pv(FwdAcc& a, const bf16* V_, const bf16x8 (
   }
 }
 
+// Dropout: zero the dropped P^T fragment elements of query q (the PV operands only: l, m and lse stay those of
+// the undropped softmax).  pf[c][4g .. 4g + 3] = keys k0 + 16c + 8g + 4 (lane >> 5) + 0..3 of the tile at k0.
+__device__ __forceinline__ void fwd_drop(bf16x8 (&pf)[4], uint64_t key, unsigned thr, int q, int k0, int lane) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      bool keep[4];
+      drop_keep4_keys(keep, key, thr, q, k0 + 16 * c + 8 * g + 4 * (lane >> 5));
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pf[c][4 * g + i] = keep[i] ? pf[c][4 * g + i] : (bf16)0.f;
+    }
+  }
+}
+
 // MX (fp8-mixed): the bf16 output is also written as OCP MX-fp8 (e4m3 q8 [B*N][H*64], E8M0 s8
 // [B*N][H*2]) -- the proj MX GEMM's A operand.  Lanes l and l ^ 32 hold the 32 d of one block of one
 // query (16 each), so a block's amax is one lane-pair exchange.
-template <bool MX>
+// DROP: dropout on the probabilities (mia_attn_fwd_dropout); c = 1 / (1 - p_eff) folds into the final 1 / l.
+template <bool MX, bool DROP = false>
 __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
                                                           float* __restrict__ lse, int N, int H, int nqb,
                                                           float scale_log2, uint8_t* __restrict__ q8,
-                                                          uint8_t* __restrict__ s8, bf16* __restrict__ qs_out) {
+                                                          uint8_t* __restrict__ s8, bf16* __restrict__ qs_out,
+                                                          DropArg<DROP> dr = {}) {
   __shared__ __attribute__((aligned(1024))) bf16 Ks[3][64 * 64];
   __shared__ __attribute__((aligned(1024))) bf16 Vs[3][64 * 64];
   const int t = threadIdx.x, lane = t & 63;
@@ -147,6 +164,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16* __restrict
 #pragma unroll
   for (int j = 0; j < 8; ++j) one[j] = (bf16)0.f;
   one[0] = (lane < 32) ? (bf16)1.f : (bf16)0.f;
+  uint64_t dkey = 0;
+  if constexpr (DROP) dkey = drop_key(dr.seed, b, hd);
   FwdAcc a;
   a.o[0] = zero16(); a.o[1] = zero16();
   a.l = 0.f; a.mb = 0.f;
@@ -167,6 +186,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16* __restrict
     fwd_qk(s, Ks[P], qf, one, a.mrow, lane);
     __builtin_amdgcn_s_setprio(1);  // the softmax's VALU issues ahead of the co-resident waves' MFMA streams
     fwd_softmax<decltype(first)::value>(s, a, pf, decltype(first)::value ? N - kt * 64 : 64, lane);
+    if constexpr (DROP) fwd_drop(pf, dkey, dr.thr, q, kt * 64, lane);
     __builtin_amdgcn_s_setprio(0);
     fwd_pv(a, Vs[P], pf, lane);
     if (ahead) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // tile j + 1's pieces have landed
@@ -182,7 +202,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16* __restrict
   tile(T{}, F{}, P0{}, 0);
   ring3_guarded<1>(1, ntiles, [&](auto tl, auto sl, int j) __attribute__((always_inline)) { tile(F{}, tl, sl, j); });
   const float lt = half_exchange_sum(a.l);
-  const float inv = 1.f / lt;
+  float inv = 1.f / lt;
+  if constexpr (DROP) inv = dr.c / lt;
   if constexpr (MX) {
     // every lane takes part in the pair exchange; queries past the end store nothing
 #pragma unroll
@@ -219,9 +240,11 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16* __restrict
   }
 }
 template __global__ void attn_fwd_kernel<false>(const bf16*, bf16*, float*, int, int, int, float, uint8_t*, uint8_t*,
-                                                bf16*);
+                                                bf16*, DropArg<false>);
 template __global__ void attn_fwd_kernel<true>(const bf16*, bf16*, float*, int, int, int, float, uint8_t*, uint8_t*,
-                                               bf16*);
+                                               bf16*, DropArg<false>);
+template __global__ void attn_fwd_kernel<false, true>(const bf16*, bf16*, float*, int, int, int, float, uint8_t*,
+                                                      uint8_t*, bf16*, DropArg<true>);
 
 
 // Key-parallel dK / dV.  One wave = 32 keys (key on the lane), 4 waves = 128 keys per block; the
@@ -233,9 +256,14 @@ constexpr int BWD_K = 128;
 
 // qvalid = queries of the tile inside the sequence (>= 64: all): a wave-uniform mask that only the peeled first
 // tile (the last query tile: the kernel walks the queries backwards) passes at run time
+// DROP (q0 = the tile's first query, key = this lane's key): P is recomputed undropped; dV takes M o P (c is applied
+// to the finished sum) and dS = P o (c M o (dO V^T) - delta).  Under the mask -delta cannot ride the dP chain, so
+// the chain stops after its four k-steps and -delta comes from an MFMA of its own (fragment row x ones).
+template <bool DROP = false>
 __device__ __forceinline__ void dkdv_tile(f32x16 (&dk)[2], f32x16 (&dv)[2], const bf16* Q_, const bf16* G_,
                                           const bf16* F_, const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], bf16x8 one,
-                                          int qvalid, int lane) {
+                                          int qvalid, int lane, uint64_t dkey = 0, unsigned thr = 0, float c = 1.f,
+                                          int q0 = 0, int key = 0) {
   // the row fragments of query half sq (Q', dO, the two fifth-k-step rows), loaded one half ahead: half 1's
   // fly under half 0's softmax and dV / dK products instead of one LDS latency in front of every MFMA
   bf16x8 fr[2][10];
@@ -264,7 +292,8 @@ __device__ __forceinline__ void dkdv_tile(f32x16 (&dk)[2], f32x16 (&dv)[2], cons
       dp = mfma(f[4 + ks], vf[ks], dp);
     }
     scs[sq] = mfma(f[8], one, sc);
-    dps[sq] = mfma(f[9], one, dp);
+    if constexpr (DROP) dps[sq] = dp;
+    else dps[sq] = mfma(f[9], one, dp);
     if (sq == 0) load(1, fr[1]);
   }
 #pragma unroll
@@ -277,8 +306,23 @@ __device__ __forceinline__ void dkdv_tile(f32x16 (&dk)[2], f32x16 (&dv)[2], cons
 #pragma unroll
       for (int r = 0; r < 16; ++r) sc[r] = ((r & 3) + 8 * (r >> 2)) < lim ? sc[r] : 0.f;
     }
+    if constexpr (DROP) {
+      const f32x16 nd = mfma(fr[sq][9], one, zero16());  // -delta of each query row
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dp[r] *= sc[r];
+      for (int g = 0; g < 4; ++g) {  // registers 4g .. 4g + 3 = queries q0 + 32 sq + 8g + 4 (lane >> 5) + 0..3
+        bool keep[4];
+        drop_keep4_queries(keep, dkey, thr, q0 + 32 * sq + 8 * g + 4 * (lane >> 5), key);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = 4 * g + i;
+          dp[r] = sc[r] * fmaf(dp[r], keep[i] ? c : 0.f, nd[r]);
+          sc[r] = keep[i] ? sc[r] : 0.f;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dp[r] *= sc[r];
+    }
 #pragma unroll
     for (int sk = 0; sk < 2; ++sk) {
       const bf16x8 pf = acc_frag(sc, sk), df = acc_frag(dp, sk);
@@ -291,10 +335,11 @@ __device__ __forceinline__ void dkdv_tile(f32x16 (&dk)[2], f32x16 (&dv)[2], cons
   }
 }
 
+template <bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
                                                                const bf16* __restrict__ qs, const bf16* __restrict__ frag,
                                                                bf16* __restrict__ dqkv, int N, int H, int nkb,
-                                                               float dk_scale) {
+                                                               float dk_scale, DropArg<DROP> dr = {}) {
   __shared__ __attribute__((aligned(1024))) bf16 Qs[2][64 * 64];
   __shared__ __attribute__((aligned(1024))) bf16 Gs[2][64 * 64];
   __shared__ __attribute__((aligned(1024))) bf16 Fs[2][64 * 16];
@@ -328,6 +373,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
   const bf16x8 one = ones3(lane);
   f32x16 dk[2], dv[2];
   dk[0] = zero16(); dk[1] = zero16(); dv[0] = zero16(); dv[1] = zero16();
+  uint64_t dkey = 0;
+  if constexpr (DROP) dkey = drop_key(dr.seed, b, hd);
   auto tile = [&](auto first, auto par, int j) __attribute__((always_inline)) {
     constexpr int P = decltype(par)::value;
     const int qt = ntiles - 1 - j;  // query tile
@@ -336,7 +383,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
       gd.issue(Gs[P ^ 1], (unsigned)(qt - 1) * tile_bytes, wave);
       fd.issue(Fs[P ^ 1], (unsigned)(qt - 1) * 64u, wave, lane);
     }
-    dkdv_tile(dk, dv, Qs[P], Gs[P], Fs[P], kf, vf, one, decltype(first)::value ? N - qt * 64 : 64, lane);
+    if constexpr (DROP)
+      dkdv_tile<true>(dk, dv, Qs[P], Gs[P], Fs[P], kf, vf, one, decltype(first)::value ? N - qt * 64 : 64, lane, dkey,
+                      dr.thr, dr.c, qt * 64, key);
+    else
+      dkdv_tile(dk, dv, Qs[P], Gs[P], Fs[P], kf, vf, one, decltype(first)::value ? N - qt * 64 : 64, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   };
@@ -362,8 +413,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const bf16* __res
     for (int i = 0; i < 4; ++i) {
       a0[i] = (bf16)(dk[0][4 * g4 + i] * dk_scale);
       a1[i] = (bf16)(dk[1][4 * g4 + i] * dk_scale);
-      c0[i] = (bf16)dv[0][4 * g4 + i];
-      c1[i] = (bf16)dv[1][4 * g4 + i];
+      if constexpr (DROP) {
+        c0[i] = (bf16)(dv[0][4 * g4 + i] * dr.c);
+        c1[i] = (bf16)(dv[1][4 * g4 + i] * dr.c);
+      } else {
+        c0[i] = (bf16)dv[0][4 * g4 + i];
+        c1[i] = (bf16)dv[1][4 * g4 + i];
+      }
     }
     *reinterpret_cast<bf16x4*>(krow + d0) = a0;
     *reinterpret_cast<bf16x4*>(krow + 32 + d0) = a1;
@@ -380,8 +436,11 @@ constexpr int BWD_Q = 128;
 
 // kvalid = keys of the tile inside the sequence (>= 64: all): a wave-uniform mask that only the peeled first
 // tile (the last key tile: the kernel walks the keys backwards) passes at run time; the loop passes 64
+// DROP (q = this lane's query, k0 = the tile's first key): dS = P o (c M o (dO V^T) - delta)
+template <bool DROP = false>
 __device__ __forceinline__ void dq_tile(f32x16 (&acc)[2], const bf16* K_, const bf16* V_, const bf16x8 (&qf)[4],
-                                        const bf16x8 (&gf)[4], float nl, float nd, int kvalid, int lane) {
+                                        const bf16x8 (&gf)[4], float nl, float nd, int kvalid, int lane,
+                                        uint64_t dkey = 0, unsigned thr = 0, float c = 1.f, int q = 0, int k0 = 0) {
   // S / dP of both key halves first: half 1's MFMAs issue before half 0's exp / dS VALU (as dkdv_tile)
   f32x16 scs[2], dps[2];
 #pragma unroll
@@ -409,8 +468,18 @@ __device__ __forceinline__ void dq_tile(f32x16 (&acc)[2], const bf16* K_, const 
 #pragma unroll
       for (int r = 0; r < 16; ++r) sc[r] = ((r & 3) + 8 * (r >> 2)) < lim ? sc[r] : 0.f;
     }
+    if constexpr (DROP) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dp[r] = (dp[r] + nd) * sc[r];
+      for (int g = 0; g < 4; ++g) {  // registers 4g .. 4g + 3 = keys k0 + 32 kh + 8g + 4 (lane >> 5) + 0..3
+        bool keep[4];
+        drop_keep4_keys(keep, dkey, thr, q, k0 + 32 * kh + 8 * g + 4 * (lane >> 5));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dp[4 * g + i] = fmaf(dp[4 * g + i], keep[i] ? c : 0.f, nd) * sc[4 * g + i];
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dp[r] = (dp[r] + nd) * sc[r];
+    }
 #pragma unroll
     for (int sk = 0; sk < 2; ++sk) {
       const bf16x8 dsf = acc_frag(dp, sk);
@@ -420,10 +489,12 @@ __device__ __forceinline__ void dq_tile(f32x16 (&acc)[2], const bf16* K_, const 
   }
 }
 
+template <bool DROP = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
                                                              const bf16* __restrict__ dout, const float* __restrict__ lse,
                                                              bf16* __restrict__ frag, bf16* __restrict__ dqkv,
-                                                             int N, int H, int nqb, float scale, float scale_log2) {
+                                                             int N, int H, int nqb, float scale, float scale_log2,
+                                                             DropArg<DROP> dr = {}) {
   __shared__ __attribute__((aligned(1024))) bf16 Ks[3][64 * 64];
   __shared__ __attribute__((aligned(1024))) bf16 Vs[3][64 * 64];
   const int t = threadIdx.x, lane = t & 63;
@@ -483,6 +554,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16* __restr
   }
   f32x16 acc[2];
   acc[0] = zero16(); acc[1] = zero16();
+  uint64_t dkey = 0;
+  if constexpr (DROP) dkey = drop_key(dr.seed, b, hd);
   // one tile in slot P of the 3-slot ring: tile j + 2's DMA flies under this tile's work and tile j + 1's
   auto tile = [&](auto first, auto slot, int j) __attribute__((always_inline)) {
     constexpr int P = decltype(slot)::value;
@@ -493,7 +566,11 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16* __restr
       kd.issue(Ks[PN], (unsigned)(kt - 2) * tile_bytes, wave);
       vd.issue(Vs[PN], (unsigned)(kt - 2) * tile_bytes, wave);
     }
-    dq_tile(acc, Ks[P], Vs[P], qf, gf, nl, nd, decltype(first)::value ? N - kt * 64 : 64, lane);
+    if constexpr (DROP)
+      dq_tile<true>(acc, Ks[P], Vs[P], qf, gf, nl, nd, decltype(first)::value ? N - kt * 64 : 64, lane, dkey, dr.thr,
+                    dr.c, q, kt * 64);
+    else
+      dq_tile(acc, Ks[P], Vs[P], qf, gf, nl, nd, decltype(first)::value ? N - kt * 64 : 64, lane);
     if (ahead) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -845,8 +922,11 @@ __global__ __launch_bounds__(512) void attn_bwd_fused_kernel(const bf16* __restr
 // in f32 for parity; one wave per query (forward, dQ) or per key (dK/dV); scores staged in LDS.
 constexpr int MAXN = 3328;
 
+// DROP: the stored probabilities are masked after the row sum, c folds into the final division
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                           float* __restrict__ lse, int N, int H, float scale) {
+                                                           float* __restrict__ lse, int N, int H, float scale,
+                                                           DropArg<DROP> dr = {}) {
   __shared__ float sc[4][MAXN];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bh = blockIdx.y, b = bh / H, hd = bh % H;
@@ -854,6 +934,8 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
   if (q >= N) return;
   const int64_t ldt = (int64_t)3 * H * D;
   const float* base = qkv + (int64_t)b * N * ldt + hd * D;
+  uint64_t dkey = 0;
+  if constexpr (DROP) dkey = drop_key(dr.seed, b, hd);
   float qv[D];
 #pragma unroll
   for (int d = 0; d < D; ++d) qv[d] = base[(int64_t)q * ldt + d] * scale;
@@ -870,13 +952,15 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
   float sum = 0.f;
   for (int k = lane; k < N; k += 64) {
     const float p = expf(sc[wave][k] - mx);
-    sc[wave][k] = p;
+    if constexpr (DROP) sc[wave][k] = drop_keep(dkey, dr.thr, q, k) ? p : 0.f;
+    else sc[wave][k] = p;
     sum += p;
   }
   sum = wave_sum(sum);
   wave_sync();
   float o = 0.f;
   for (int k = 0; k < N; ++k) o = fmaf(sc[wave][k], base[(int64_t)k * ldt + 2 * H * D + lane], o);
+  if constexpr (DROP) o *= dr.c;
   out[((int64_t)b * N + q) * H * D + hd * D + lane] = o / sum;
   if (lane == 0) lse[(int64_t)bh * N + q] = mx + logf(sum);
 }
@@ -894,10 +978,11 @@ __global__ void attn_delta_f32_kernel(const float* __restrict__ out, const float
   }
 }
 
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                               const float* __restrict__ lse,
                                                               const float* __restrict__ delta, float* __restrict__ dqkv,
-                                                              int N, int H, float scale) {
+                                                              int N, int H, float scale, DropArg<DROP> dr = {}) {
   __shared__ float sc[4][MAXN];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bh = blockIdx.y, b = bh / H, hd = bh % H;
@@ -912,6 +997,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __res
     gv[d] = dout[((int64_t)b * N + q) * ldo + hd * D + d];
   }
   const float L = lse[(int64_t)bh * N + q], dl = delta[(int64_t)bh * N + q];
+  uint64_t dkey = 0;
+  if constexpr (DROP) dkey = drop_key(dr.seed, b, hd);
   for (int k = lane; k < N; k += 64) {
     const float* kr = base + (int64_t)k * ldt + H * D;
     const float* vr = kr + H * D;
@@ -919,7 +1006,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __res
 #pragma unroll
     for (int d = 0; d < D; ++d) { s = fmaf(qv[d], kr[d], s); dp = fmaf(gv[d], vr[d], dp); }
     const float p = expf(s - L);
-    sc[wave][k] = p * (dp - dl);
+    if constexpr (DROP) sc[wave][k] = p * ((drop_keep(dkey, dr.thr, q, k) ? dr.c * dp : 0.f) - dl);
+    else sc[wave][k] = p * (dp - dl);
   }
   wave_sync();
   float a = 0.f;
@@ -927,11 +1015,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __res
   dqkv[((int64_t)b * N + q) * ldt + hd * D + lane] = a * scale;
 }
 
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv_f32_kernel(const float* __restrict__ qkv,
                                                                 const float* __restrict__ dout,
                                                                 const float* __restrict__ lse,
                                                                 const float* __restrict__ delta,
-                                                                float* __restrict__ dqkv, int N, int H, float scale) {
+                                                                float* __restrict__ dqkv, int N, int H, float scale,
+                                                                DropArg<DROP> dr = {}) {
   __shared__ float sp[4][MAXN];
   __shared__ float sd[4][MAXN];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -946,6 +1036,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_f32_kernel(const float* __r
     kv[d] = base[(int64_t)k * ldt + H * D + d] * scale;
     vv[d] = base[(int64_t)k * ldt + 2 * H * D + d];
   }
+  uint64_t dkey = 0;
+  if constexpr (DROP) dkey = drop_key(dr.seed, b, hd);
   for (int q = lane; q < N; q += 64) {
     const float* qr = base + (int64_t)q * ldt;
     const float* gr = dout + ((int64_t)b * N + q) * ldo + hd * D;
@@ -953,8 +1045,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_f32_kernel(const float* __r
 #pragma unroll
     for (int d = 0; d < D; ++d) { s = fmaf(kv[d], qr[d], s); dp = fmaf(vv[d], gr[d], dp); }
     const float p = expf(s - lse[(int64_t)bh * N + q]);
-    sp[wave][q] = p;
-    sd[wave][q] = p * (dp - delta[(int64_t)bh * N + q]);
+    if constexpr (DROP) {
+      const float m = drop_keep(dkey, dr.thr, q, k) ? dr.c : 0.f;
+      sp[wave][q] = p * m;
+      sd[wave][q] = p * (m * dp - delta[(int64_t)bh * N + q]);
+    } else {
+      sp[wave][q] = p;
+      sd[wave][q] = p * (dp - delta[(int64_t)bh * N + q]);
+    }
   }
   wave_sync();
   float dv = 0.f, dk = 0.f;
@@ -1037,9 +1135,19 @@ extern "C" int64_t mia_attn_bwd_error_offset(int32_t B, int32_t N, int32_t H) {
   return fb_flags_offset(B, N, H) + (int64_t)B * H * cdiv(N, 64) * 16;
 }
 
+// 16-bit keep threshold of a dropout rate (0 = no dropout: the undropped kernels run)
+static unsigned drop_thr(float p) { return (unsigned)std::min<long>(lrintf(p * 65536.f), 65535); }
+static DropArg<true> drop_arg(unsigned thr, uint64_t seed) {
+  DropArg<true> d;
+  d.seed = seed;
+  d.thr = thr;
+  d.c = (float)(65536.0 / (65536.0 - (double)thr));
+  return d;
+}
+
 static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                          void* work, int32_t dtype, int32_t B, int32_t N, int32_t H, float scale, int q_ready,
-                         int fused, mia_stream_t stream) {
+                         int fused, mia_stream_t stream, unsigned thr = 0, uint64_t seed = 0) {
   MIA_CHECK_ARG(qkv && out && dout && lse && dqkv && work, "attn_bwd: null pointer");
   MIA_CHECK_ARG(B > 0 && N > 0 && H > 0 && (int64_t)B * H < 65536, "attn_bwd: bad shape");
   hipStream_t s = as_stream(stream);
@@ -1051,6 +1159,16 @@ static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, con
         (const float*)out, (const float*)dout, delta, B, N, H);
     MIA_LAUNCH_CHECK("attn_delta_f32");
     dim3 g4((unsigned)cdiv(N, 4), (unsigned)(B * H));
+    if (thr) {
+      const DropArg<true> dr = drop_arg(thr, seed);
+      attn_bwd_dq_f32_kernel<true><<<g4, 256, 0, s>>>((const float*)qkv, (const float*)dout, lse, delta,
+                                                      (float*)dqkv, N, H, scale, dr);
+      MIA_LAUNCH_CHECK("attn_bwd_dq_f32_drop");
+      attn_bwd_dkdv_f32_kernel<true><<<g4, 256, 0, s>>>((const float*)qkv, (const float*)dout, lse, delta,
+                                                        (float*)dqkv, N, H, scale, dr);
+      MIA_LAUNCH_CHECK("attn_bwd_dkdv_f32_drop");
+      return 0;
+    }
     attn_bwd_dq_f32_kernel<<<g4, 256, 0, s>>>((const float*)qkv, (const float*)dout, lse, delta, (float*)dqkv, N, H,
                                               scale);
     MIA_LAUNCH_CHECK("attn_bwd_dq_f32");
@@ -1092,6 +1210,17 @@ static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, con
     return 0;
   }
   const int nkb = (int)cdiv(N, BWD_K), nqb = (int)cdiv(N, BWD_Q);
+  if (thr) {
+    const DropArg<true> dr = drop_arg(thr, seed);
+    attn_bwd_dq_kernel<true><<<(unsigned)(nqb * B * H), 256, 0, s>>>((const bf16*)qkv, (const bf16*)out,
+                                                                     (const bf16*)dout, lse, frag, (bf16*)dqkv, N, H,
+                                                                     nqb, scale, scale_log2, dr);
+    MIA_LAUNCH_CHECK("attn_bwd_dq_drop");
+    attn_bwd_dkdv_kernel<true><<<(unsigned)(nkb * B * H), 256, 0, s>>>((const bf16*)qkv, (const bf16*)dout, qs, frag,
+                                                                       (bf16*)dqkv, N, H, nkb, 1.f / LOG2E, dr);
+    MIA_LAUNCH_CHECK("attn_bwd_dkdv_drop");
+    return 0;
+  }
   attn_bwd_dq_kernel<<<(unsigned)(nqb * B * H), 256, 0, s>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout,
                                                              lse, frag, (bf16*)dqkv, N, H, nqb, scale, scale_log2);
   MIA_LAUNCH_CHECK("attn_bwd_dq");
@@ -1150,4 +1279,49 @@ extern "C" int mia_attn_fwd_save_q(const void* qkv, void* out, float* lse, void*
 extern "C" int mia_attn_bwd_saved_q(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                     void* work, int32_t B, int32_t N, int32_t H, float scale, mia_stream_t stream) {
   return attn_bwd_impl(qkv, out, dout, lse, dqkv, work, MIA_BF16, B, N, H, scale, 1, 0, stream);
+}
+
+// Attention with dropout on the probabilities (nn.MultiheadAttention(dropout=p) in training mode): the keep mask
+// is the pure function keep(seed, b, h, q, k) documented in attn_common.h, p is quantised to p_eff = round(p *
+// 65536) / 65536 and the kept probabilities are scaled by 1 / (1 - p_eff).  lse is that of the undropped softmax.
+// bf16: the flash forward (work non-null: it also saves Q', as mia_attn_fwd_save_q) and the two-kernel backward;
+// f32: the exact kernels.  p_drop = 0 (or one that rounds to p_eff = 0) runs the existing entry points.
+extern "C" int mia_attn_fwd_dropout(const void* qkv, void* out, float* lse, void* work, int32_t dtype, int32_t B,
+                                    int32_t N, int32_t H, float scale, float p_drop, uint64_t seed,
+                                    mia_stream_t stream) {
+  MIA_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "attn_fwd_dropout: p_drop must be in [0, 1)");
+  const unsigned thr = drop_thr(p_drop);
+  if (thr == 0) {
+    if (dtype == MIA_BF16 && work) return mia_attn_fwd_save_q(qkv, out, lse, nullptr, nullptr, work, B, N, H, scale, stream);
+    return mia_attn_fwd(qkv, out, lse, dtype, B, N, H, scale, stream);
+  }
+  MIA_CHECK_ARG(qkv && out && lse, "attn_fwd_dropout: null pointer");
+  MIA_CHECK_ARG(B > 0 && N > 0 && H > 0 && (int64_t)B * H < 65536, "attn_fwd_dropout: bad shape");
+  const DropArg<true> dr = drop_arg(thr, seed);
+  if (dtype == MIA_F32) {
+    MIA_CHECK_ARG(N <= MAXN, "attn_fwd_dropout f32: N must be <= %d", MAXN);
+    attn_fwd_f32_kernel<true><<<dim3((unsigned)cdiv(N, 4), (unsigned)(B * H)), 256, 0, as_stream(stream)>>>(
+        (const float*)qkv, (float*)out, lse, N, H, scale, dr);
+    MIA_LAUNCH_CHECK("attn_fwd_f32_drop");
+    return 0;
+  }
+  MIA_CHECK_ARG(dtype == MIA_BF16, "attn_fwd_dropout: dtype");
+  MIA_CHECK_ARG((int64_t)N * 3 * H * D * 2 < (1ll << 31), "attn_fwd_dropout: one sequence must span < 2 GiB");
+  MIA_CHECK_ARG((reinterpret_cast<uintptr_t>(work) & 15) == 0, "attn_fwd_dropout: work must be 16-B aligned");
+  const int nqb = (int)cdiv(N, FWD_Q);
+  MIA_CHECK_ARG((int64_t)nqb * B * H < (1ll << 31), "attn_fwd_dropout: grid too large");
+  attn_fwd_kernel<false, true><<<(unsigned)(nqb * B * H), 256, 0, as_stream(stream)>>>(
+      (const bf16*)qkv, (bf16*)out, lse, N, H, nqb, scale * LOG2E, nullptr, nullptr, (bf16*)work, dr);
+  MIA_LAUNCH_CHECK("attn_fwd_drop");
+  return 0;
+}
+
+// the backward of mia_attn_fwd_dropout (same p_drop and seed); work: mia_attn_bwd_workspace_bytes(dtype, ...) or,
+// bf16, mia_attn_saved_q_bytes; q_ready (bf16): the forward wrote Q' into `work`
+extern "C" int mia_attn_bwd_dropout(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+                                    void* work, int32_t dtype, int32_t B, int32_t N, int32_t H, float scale,
+                                    float p_drop, uint64_t seed, int32_t q_ready, mia_stream_t stream) {
+  MIA_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "attn_bwd_dropout: p_drop must be in [0, 1)");
+  return attn_bwd_impl(qkv, out, dout, lse, dqkv, work, dtype, B, N, H, scale, dtype == MIA_BF16 ? q_ready : 0, 0,
+                       stream, drop_thr(p_drop), seed);
 }

@@ -380,6 +380,55 @@ struct FragDMA {
 // the zero half of the ones fragment, so its (finite) copy of the row contributes nothing.
 __device__ __forceinline__ bf16x8 row_frag(const bf16* row) { return *reinterpret_cast<const bf16x8*>(row); }
 
+// ------------------------------------------------------------------------------ dropout on P
+// keep(seed, b, h, q, k), a pure function of its five arguments (no tiling, shape or dtype in it):
+//   key  = splitmix64(seed ^ splitmix64((u64(b) << 32) | h))                     per (b, h)
+//   w    = splitmix64(key ^ ((u64(q >> 1) << 32) | u64(k >> 1)))                 per 2 x 2 (query, key) cell
+//   u16  = (w >> (32 (q & 1) + 16 (k & 1))) & 0xffff
+//   keep = u16 >= thr,  thr = round(p * 65536) (at most 65535),  p_eff = thr / 65536,  c = 1 / (1 - p_eff)
+// One 64-bit hash serves four elements, and both register layouts use all of them: a lane of the forward / dQ
+// kernels holds 4 consecutive keys of one query (two cells, the 32-bit word of its query parity from each); a
+// lane of the dK/dV kernel holds 4 consecutive queries of one key (two cells, the 16-bit field of its key parity
+// from both words).  tests/_ast_small_ref.py restates it in numpy.
+template <bool DROP>
+struct DropArg {};
+template <>
+struct DropArg<true> {
+  uint64_t seed;
+  unsigned thr;  // 16-bit keep threshold
+  float c;       // 1 / (1 - thr / 65536)
+};
+
+__device__ __forceinline__ uint64_t drop_key(uint64_t seed, int b, int h) {
+  return splitmix64(seed ^ splitmix64(((uint64_t)(unsigned)b << 32) | (uint64_t)(unsigned)h));
+}
+__device__ __forceinline__ uint64_t drop_cell(uint64_t key, int q2, int k2) {
+  return splitmix64(key ^ (((uint64_t)(unsigned)q2 << 32) | (uint64_t)(unsigned)k2));
+}
+__device__ __forceinline__ bool drop_keep(uint64_t key, unsigned thr, int q, int k) {
+  return ((unsigned)(drop_cell(key, q >> 1, k >> 1) >> (32 * (q & 1) + 16 * (k & 1))) & 0xffffu) >= thr;
+}
+// keep[i] of keys k0 .. k0 + 3 (k0 % 4 == 0) of query q
+__device__ __forceinline__ void drop_keep4_keys(bool (&keep)[4], uint64_t key, unsigned thr, int q, int k0) {
+  const int sh = 32 * (q & 1);
+  const unsigned w0 = (unsigned)(drop_cell(key, q >> 1, k0 >> 1) >> sh);
+  const unsigned w1 = (unsigned)(drop_cell(key, q >> 1, (k0 >> 1) + 1) >> sh);
+  keep[0] = (w0 & 0xffffu) >= thr;
+  keep[1] = (w0 >> 16) >= thr;
+  keep[2] = (w1 & 0xffffu) >= thr;
+  keep[3] = (w1 >> 16) >= thr;
+}
+// keep[i] of queries q0 .. q0 + 3 (q0 % 4 == 0) of key k
+__device__ __forceinline__ void drop_keep4_queries(bool (&keep)[4], uint64_t key, unsigned thr, int q0, int k) {
+  const int sh = 16 * (k & 1);
+  const uint64_t a = drop_cell(key, q0 >> 1, k >> 1) >> sh;
+  const uint64_t b = drop_cell(key, (q0 >> 1) + 1, k >> 1) >> sh;
+  keep[0] = ((unsigned)a & 0xffffu) >= thr;
+  keep[1] = ((unsigned)(a >> 32) & 0xffffu) >= thr;
+  keep[2] = ((unsigned)b & 0xffffu) >= thr;
+  keep[3] = ((unsigned)(b >> 32) & 0xffffu) >= thr;
+}
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned fb_ld_flag(const unsigned* p) {

@@ -321,6 +321,19 @@ __global__ void dropout_kernel(void* x, int dtype, int64_t n, float p, uint64_t 
   }
 }
 
+// dst = (res ? res : 0) + dropout(src): mia_dropout's keep rule and scaling on the same element index; each
+// element is read before it is written, so src == dst is allowed
+__global__ void dropout_apply_kernel(const void* src, int sd, const float* res, void* dst, int dd, int64_t n, float p,
+                                     uint64_t seed) {
+  const float scale = 1.f / (1.f - p);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float u = hash_u01(seed, (uint64_t)i);
+    float v = u >= p ? ld_elem(src, sd, i) * scale : 0.f;
+    if (res) v += res[i];
+    st_elem(dst, dd, i, v);
+  }
+}
+
 __global__ void cast_kernel(const void* src, int sd, void* dst, int dd, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     st_elem(dst, dd, i, ld_elem(src, sd, i));
@@ -689,6 +702,17 @@ extern "C" int mia_dropout(void* x, int32_t dtype, int64_t numel, float p, uint6
   if (p == 0.f || numel == 0) return 0;
   dropout_kernel<<<blocks_for(numel), 256, 0, as_stream(stream)>>>(x, dtype, numel, p, seed);
   MIA_LAUNCH_CHECK("dropout");
+  return 0;
+}
+
+extern "C" int mia_dropout_apply(const void* src, int32_t sdtype, const float* res, void* dst, int32_t ddtype,
+                                 int64_t numel, float p, uint64_t seed, mia_stream_t stream) {
+  MIA_CHECK_ARG(src && dst && p >= 0.f && p < 1.f, "dropout_apply: args");
+  MIA_CHECK_ARG((sdtype == MIA_F32 || sdtype == MIA_BF16) && (ddtype == MIA_F32 || ddtype == MIA_BF16),
+                "dropout_apply: dtype");
+  if (numel == 0) return 0;
+  dropout_apply_kernel<<<blocks_for(numel), 256, 0, as_stream(stream)>>>(src, sdtype, res, dst, ddtype, numel, p, seed);
+  MIA_LAUNCH_CHECK("dropout_apply");
   return 0;
 }
 

@@ -143,6 +143,9 @@ SIGNATURES = {
     "mia_attn_bwd_two_pass": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]),
     "mia_attn_bwd_fused": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]),
     "mia_attn_bwd_error_offset": (C.c_int64, [i32, i32, i32]),
+    "mia_attn_fwd_dropout": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, C.c_uint64, vp]),
+    "mia_attn_bwd_dropout": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, C.c_uint64, i32, vp]),
+    "mia_dropout_apply": (C.c_int, [vp, i32, vp, vp, i32, i64, f32, C.c_uint64, vp]),
     "mia_stream_copy": (C.c_int, [vp, vp, i64, vp]),
     "mia_mfma_rate_sink_floats": (i64, [i32]),
     "mia_mfma_rate": (C.c_int, [vp, i32, i32, vp]),

@@ -9,9 +9,18 @@ dtype.  fc1's epilogue writes both gelu(u) (fc2's operand) and the derivative ge
 the fc2 dgrad GEMM (MIA_DACT_MUL); residual adds are GEMM epilogues (MIA_ACT_ADD_AUX / accumulate).  In bf16 mode the
 linear weights are cast to bf16 once per step and every GEMM operand is bf16, so the projections run
 on the LDS-DMA dense kernel (mia_gemm path 5).
+
+The small-AST family (src/models/ast_small.py, ast_mini.py: blocks on nn.MultiheadAttention(dropout=p) and
+Linear-GELU-Dropout-Linear-Dropout) runs through the same node.  What differs is read from the model, every
+default being ASTModel's: ``ln_eps`` (1e-6), the training-mode dropout rates ``attn_drop`` (on the attention
+probabilities, inside the attention kernels: mia_attn_fwd_dropout / mia_attn_bwd_dropout), ``act_drop`` (after
+GELU) and ``out_drop`` (after fc2; both mia_dropout_apply), 0 each, and ``dropout_seeds`` (None: per-call seeds from
+a counter; a (depth, 3) table pins them -- the tests' hook).  In eval mode or with all rates 0 the calls are
+exactly ASTModel's.
 """
 from __future__ import annotations
 
+import itertools
 import os
 
 import torch
@@ -20,9 +29,32 @@ from ..miaudio import kernels as K
 from ..miaudio import lib as L
 
 EPS = 1e-6
+_SEED = itertools.count(0xA57D)
 
 
-def _ln(x, g, b, out_dtype, rows, D, mx: bool = False):
+def _dropout_plan(model, nb):
+    """None (eval mode or all rates 0: the undropped calls), or ((p_attn, p_act, p_out), [(seed_attn, seed_act,
+    seed_out)] per block): pinned by model.dropout_seeds, else fresh from the counter for this call."""
+    if not model.training:
+        return None
+    rates = tuple(float(getattr(model, n, 0.0)) for n in ("attn_drop", "act_drop", "out_drop"))
+    if not any(rates):
+        return None
+    pinned = getattr(model, "dropout_seeds", None)
+    if pinned is not None:
+        seeds = [tuple(int(pinned[i][j]) & ((1 << 64) - 1) for j in range(3)) for i in range(nb)]
+    else:
+        seeds = [tuple(next(_SEED) * 0x9E3779B1 for _ in range(3)) for _ in range(nb)]
+    return rates, seeds
+
+
+def _dropout_apply(src, res, dst, p, seed):
+    """dst = (res or 0) + dropout(src) (mia_dropout_apply; src may be dst)"""
+    L.check(L.load().mia_dropout_apply(src.data_ptr(), L.dtype_code(src), L.ptr(res), dst.data_ptr(),
+                                       L.dtype_code(dst), src.numel(), p, seed, L.stream_ptr()), "mia_dropout_apply")
+
+
+def _ln(x, g, b, out_dtype, rows, D, mx: bool = False, eps: float = EPS):
     """LayerNorm forward -> (y, mean, rstd[, MX-fp8 copy of y when mx: mia_layernorm_fwd_mx])."""
     y = torch.empty(rows, D, dtype=out_dtype, device=x.device)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
@@ -31,10 +63,10 @@ def _ln(x, g, b, out_dtype, rows, D, mx: bool = False):
         yq = K.mx_empty(rows, D, x.device)
         L.check(L.load().mia_layernorm_fwd_mx(x.data_ptr(), L.dtype_code(x), g.data_ptr(), b.data_ptr(), y.data_ptr(),
                                               yq.q.data_ptr(), yq.scales.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                              rows, D, EPS, L.stream_ptr()), "mia_layernorm_fwd_mx")
+                                              rows, D, eps, L.stream_ptr()), "mia_layernorm_fwd_mx")
         return y, mean, rstd, yq
     L.check(L.load().mia_layernorm_fwd(x.data_ptr(), L.dtype_code(x), g.data_ptr(), b.data_ptr(), y.data_ptr(),
-                                       L.dtype_code(y), mean.data_ptr(), rstd.data_ptr(), rows, D, EPS, L.stream_ptr()),
+                                       L.dtype_code(y), mean.data_ptr(), rstd.data_ptr(), rows, D, eps, L.stream_ptr()),
             "mia_layernorm_fwd")
     return y, mean, rstd, None
 
@@ -66,6 +98,15 @@ def _ln_bwd(dy, x, g, mean, rstd, dx, rows, D, accumulate: bool, dx2=None, dx2_m
                                              dg.data_ptr(), db.data_ptr(), cs.data_ptr(), ws.data_ptr(), rows, D,
                                              L.stream_ptr()), "mia_layernorm_bwd_colsum")
         return dg, db, cs
+    if dx2 is not None and dx2.dtype != dx.dtype:
+        # widths other than 768 take the generic kernel, which writes no second copy: a cast pass of the updated dx
+        L.check(lib.mia_layernorm_bwd(dy.data_ptr(), L.dtype_code(dy), x.data_ptr(), L.dtype_code(x), g.data_ptr(),
+                                      mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), L.dtype_code(dx),
+                                      int(accumulate), None, 0, dg.data_ptr(), db.data_ptr(), ws.data_ptr(), rows, D,
+                                      L.stream_ptr()), "mia_layernorm_bwd")
+        L.check(lib.mia_cast(dx.data_ptr(), L.dtype_code(dx), dx2.data_ptr(), L.dtype_code(dx2), dx.numel(),
+                             L.stream_ptr()), "mia_cast")
+        return dg, db, None
     L.check(lib.mia_layernorm_bwd(dy.data_ptr(), L.dtype_code(dy), x.data_ptr(), L.dtype_code(x), g.data_ptr(),
                                   mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), L.dtype_code(dx), int(accumulate),
                                   L.ptr(dx2), L.dtype_code(dx2) if dx2 is not None else 0, dg.data_ptr(),
@@ -162,7 +203,11 @@ class ASTFunction(torch.autograd.Function):
             L.check(L.load().mia_tokens_fwd(patches.data_ptr(), cls.data_ptr(), pos.data_ptr(), x.data_ptr(), B, Np,
                                             D, L.stream_ptr()), "mia_tokens_fwd")
         saved_blocks = []
-        nb = len(model.transformer)
+        nb = (len(params) - 8) // 12
+        eps = float(getattr(model, "ln_eps", EPS))
+        plan = _dropout_plan(model, nb)
+        if plan is not None and mx:
+            raise ValueError("dropout inside the blocks is not available on the MX-fp8 path (these models run bf16)")
         scale = (D // Hh) ** -0.5
         wcast = []
         for i in range(nb):
@@ -181,7 +226,9 @@ class ASTFunction(torch.autograd.Function):
                     kw.pop("mx", None)
                     _linear(xin, W, bias, out, Tt, cd, tag=tag, **kw)
 
-            h, m1, r1, hq = _ln(x, g1, b1, tdt, Tt, D, mx=mx)
+            p_attn, p_act, p_out = plan[0] if plan is not None else (0.0, 0.0, 0.0)
+            s_attn, s_act, s_out = plan[1][i] if plan is not None else (0, 0, 0)
+            h, m1, r1, hq = _ln(x, g1, b1, tdt, Tt, D, mx=mx, eps=eps)
             qkv = torch.empty(Tt, 3 * D, dtype=tdt, device=dev)
             lin(h, hq, 0, wqkv, bqkv, qkv, "qkv.fwd")
             a = torch.empty(Tt, D, dtype=tdt, device=dev)
@@ -195,7 +242,11 @@ class ASTFunction(torch.autograd.Function):
                 # backward's running dQ sums are the backward's own transient workspace
                 aw = torch.empty(int(L.load().mia_attn_saved_q_bytes(B, N, Hh)), dtype=torch.uint8, device=dev)
             with K.probe("attn.fwd", 4.0 * B * Hh * N * N * (D // Hh), (qkv.numel() + a.numel()) * qkv.element_size()):
-                if aw is not None:
+                if p_attn > 0:  # dropout on the probabilities, inside the kernel (aw: it also saves Q')
+                    L.check(L.load().mia_attn_fwd_dropout(qkv.data_ptr(), a.data_ptr(), lse.data_ptr(), L.ptr(aw), cd,
+                                                          B, N, Hh, scale, p_attn, s_attn, L.stream_ptr()),
+                            "mia_attn_fwd_dropout")
+                elif aw is not None:
                     L.check(L.load().mia_attn_fwd_save_q(qkv.data_ptr(), a.data_ptr(), lse.data_ptr(),
                                                          aq.q.data_ptr() if mx else None,
                                                          aq.scales.data_ptr() if mx else None, aw.data_ptr(), B, N,
@@ -209,21 +260,28 @@ class ASTFunction(torch.autograd.Function):
                                                   L.stream_ptr()), "mia_attn_fwd")
             xm = torch.empty(Tt, D, dtype=torch.float32, device=dev)
             lin(a, aq, 1, wproj, bproj, xm, "proj.fwd", act=L.ACT_ADD_AUX, aux=x)
-            h2, m2, r2, h2q = _ln(xm, g2, b2, tdt, Tt, D, mx=mx)
+            h2, m2, r2, h2q = _ln(xm, g2, b2, tdt, Tt, D, mx=mx, eps=eps)
             gd = torch.empty(Tt, w1.shape[0], dtype=tdt, device=dev)  # gelu'(u), u = fc1's pre-activation
             gu = torch.empty(Tt, w1.shape[0], dtype=tdt, device=dev)  # gelu(u)
             guq = K.mx_empty(Tt, w1.shape[0], dev) if mx else None
             lin(h2, h2q, 2, w1, bb1, gu, "fc1.fwd", act=L.ACT_GELU_SAVE_D, aux=gd, mx=guq)
+            if p_act > 0:  # one mask on gelu(u) and on gelu'(u): the MIA_DACT_MUL backward stays as it is
+                _dropout_apply(gu, None, gu, p_act, s_act)
+                _dropout_apply(gd, None, gd, p_act, s_act)
             xo = torch.empty(Tt, D, dtype=torch.float32, device=dev)
-            lin(gu, guq, 3, w2, bb2, xo, "fc2.fwd", act=L.ACT_ADD_AUX, aux=xm)
+            if p_out > 0:  # xo = xm + dropout(fc2 out): the GEMM without its residual add, then one pass in place
+                lin(gu, guq, 3, w2, bb2, xo, "fc2.fwd")
+                _dropout_apply(xo, xm, xo, p_out, s_out)
+            else:
+                lin(gu, guq, 3, w2, bb2, xo, "fc2.fwd", act=L.ACT_ADD_AUX, aux=xm)
             del hq, aq, h2q, guq
             saved_blocks.append(dict(x=x, m1=m1, r1=r1, h=h, qkv=qkv, a=a, lse=lse, xm=xm, m2=m2, r2=r2, h2=h2, gd=gd,
-                                     gu=gu, attn_work=aw))
+                                     gu=gu, attn_work=aw, drop=(p_attn, p_out, s_attn, s_out)))
             x = xo
         # final norm only matters for the CLS rows (ast.py:62-63 takes x[:, 0])
         gn, bn_, wh, bh = params[4 + 12 * nb: 8 + 12 * nb]
         xc = x.view(B, N, D)[:, 0].contiguous()
-        hc, mc, rc, _ = _ln(xc, gn, bn_, torch.float32, B, D)
+        hc, mc, rc, _ = _ln(xc, gn, bn_, torch.float32, B, D, eps=eps)
         z = torch.empty(B, wh.shape[0], dtype=torch.float32, device=dev)
         _linear(hc, wh, bh, z, B, cd, tag="head.fwd")
         probs = torch.sigmoid(z)
@@ -240,7 +298,7 @@ class ASTFunction(torch.autograd.Function):
         tdt = L.torch_dtype(cd)
         dev = dprobs.device
         Tt = B * N
-        nb = len(model.transformer)
+        nb = (len(p) - 8) // 12
         grads = [None] * len(p)
         ready = getattr(model, "_grad_ready", None)
 
@@ -295,9 +353,17 @@ class ASTFunction(torch.autograd.Function):
             du = torch.empty(Tt, w1.shape[0], dtype=tdt, device=dev)
             du_mx = K.mx_empty(Tt, w1.shape[0], dev) if "fc2" in wt and "fc1" in wt else None
             db1_ = torch.empty(w1.shape[0], dtype=torch.float32, device=dev)  # fc1 bias grad = colsum(du)
-            dW2, db2_ = _linear_bwd(dxb, sb["gu"], w2, Tt, cd, dx_out=du, dact=L.DACT_MUL, dact_aux=sb["gd"],
-                                    tag="fc2", db=db_next, dx_colsum=db1_, wt_mx=wt.get("fc2"), dy_mx=dxb_mx,
-                                    dx_mx=du_mx)
+            p_attn, p_out, s_attn, s_out = sb["drop"]
+            dy2, db2_in = dxb, db_next
+            if p_out > 0:
+                # fc2's dy is the masked copy of the residual gradient; its bias gradient is the column sum of
+                # THAT (from the weight-gradient GEMM), not the unmasked sum the LayerNorm backward handed over
+                dy2, db2_in = torch.empty_like(dxb), None
+                _dropout_apply(dxb, None, dy2, p_out, s_out)
+            dW2, db2_ = _linear_bwd(dy2, sb["gu"], w2, Tt, cd, dx_out=du, dact=L.DACT_MUL, dact_aux=sb["gd"],
+                                    tag="fc2", db=db2_in, dx_colsum=db1_, wt_mx=wt.get("fc2"),
+                                    dy_mx=dxb_mx if p_out == 0 else None, dx_mx=du_mx)
+            del dy2
             dh2 = torch.empty(Tt, D, dtype=tdt, device=dev)
             dW1, db1_ = _linear_bwd(du, sb["h2"], w1, Tt, cd, dx_out=dh2, tag="fc1", db=db1_, wt_mx=wt.get("fc1"),
                                     dy_mx=du_mx)
@@ -316,7 +382,16 @@ class ASTFunction(torch.autograd.Function):
             work = sb["attn_work"]
             with K.probe("attn.bwd", 8.0 * B * Hh * N * N * (D // Hh),  # 2x fwd, recompute not credited
                          (2 * dqkv.numel() + 2 * da.numel()) * dqkv.element_size()):
-                if work is not None and ATTN_ONEPASS:  # Q' already written by the forward
+                if p_attn > 0:  # the two-kernel backward under the forward's mask (same rate and seed)
+                    q_ready = int(work is not None)
+                    if work is None:
+                        work = torch.empty(int(L.load().mia_attn_bwd_workspace_bytes(cd, B, N, Hh)), dtype=torch.uint8,
+                                           device=dev)
+                    L.check(L.load().mia_attn_bwd_dropout(sb["qkv"].data_ptr(), sb["a"].data_ptr(), da.data_ptr(),
+                                                          sb["lse"].data_ptr(), dqkv.data_ptr(), work.data_ptr(), cd, B,
+                                                          N, Hh, s["scale"], p_attn, s_attn, q_ready, L.stream_ptr()),
+                            "mia_attn_bwd_dropout")
+                elif work is not None and ATTN_ONEPASS:  # Q' already written by the forward
                     chain = torch.empty(int(L.load().mia_attn_bwd_chain_bytes(B, N, Hh)), dtype=torch.uint8, device=dev)
                     L.check(L.load().mia_attn_bwd_onepass(sb["qkv"].data_ptr(), sb["a"].data_ptr(), da.data_ptr(),
                                                           sb["lse"].data_ptr(), dqkv.data_ptr(), work.data_ptr(),

@@ -460,6 +460,11 @@ int mia_splitk_reduce(const float* ws, int32_t split_k, int64_t M, int64_t N,
  * nn.Dropout (envnet_v2.py:53,57).  Output scaled by 1/(1-p). */
 int mia_dropout(void* x, int32_t dtype, int64_t numel, float p, uint64_t seed,
                 mia_stream_t stream);
+/* dst = (res ? res : 0) + dropout(src) with mia_dropout's keep rule, indexing and 1/(1-p) scaling (same bits for
+ * the same seed); src / dst f32 or bf16, res f32 (numel) or NULL; src == dst is allowed.  nn.Dropout inside the
+ * small-AST MLP (ast_small.py:28,30): on gelu(u) and gelu'(u) with one seed, and as the fc2 residual add. */
+int mia_dropout_apply(const void* src, int32_t sdtype, const float* res, void* dst, int32_t ddtype, int64_t numel,
+                      float p, uint64_t seed, mia_stream_t stream);
 
 /* Soft-label loss of LitClassifier._step (engine.py:175-176):
  *   loss = -mean_b sum_c y*log(softmax(z)+1e-8);  dz written (scaled by grad_scale).
@@ -579,6 +584,24 @@ int mia_attn_bwd_fused(const void* qkv, const void* out, const void* dout, const
 int64_t mia_attn_bwd_chain_bytes(int32_t B, int32_t N, int32_t H);
 int mia_attn_bwd_onepass(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                          void* saved, void* chain, uint32_t* err, int32_t B, int32_t N, int32_t H, float scale,
+                         int32_t q_ready, mia_stream_t stream);
+/* Attention with dropout on the probabilities (nn.MultiheadAttention(dropout=p) in training mode; reference
+ * src/models/ast_small.py:22, ast_mini.py:22).  The keep mask is a pure function of (seed, b, h, q, k), the same in
+ * every kernel, dtype, tiling and launch shape:
+ *   key  = splitmix64(seed ^ splitmix64((u64(b) << 32) | h))
+ *   w    = splitmix64(key ^ ((u64(q >> 1) << 32) | u64(k >> 1)))        (one hash per 2 x 2 query x key cell)
+ *   keep = ((w >> (32 (q & 1) + 16 (k & 1))) & 0xffff) >= thr,   thr = min(round(p_drop * 65536), 65535)
+ * with splitmix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31.  The rate is quantised to p_eff = thr / 65536
+ * (|p_eff - p_drop| < 8e-6) and kept probabilities are scaled by 1 / (1 - p_eff); lse is that of the undropped
+ * softmax.  dtype MIA_BF16: the flash forward (work non-NULL: it also writes Q' as mia_attn_fwd_save_q does, at
+ * least mia_attn_saved_q_bytes) and the two-kernel backward (q_ready: `work` holds the forward's Q'); dtype
+ * MIA_F32: the exact kernels (work: forward unused, backward mia_attn_bwd_workspace_bytes).  p_drop = 0 runs
+ * mia_attn_fwd / mia_attn_fwd_save_q / the two-kernel mia_attn_bwd unchanged. */
+int mia_attn_fwd_dropout(const void* qkv, void* out, float* lse, void* work, int32_t dtype, int32_t B, int32_t N,
+                         int32_t H, float scale, float p_drop, uint64_t seed, mia_stream_t stream);
+int mia_attn_bwd_dropout(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, void* work,
+                         int32_t dtype, int32_t B, int32_t N, int32_t H, float scale, float p_drop, uint64_t seed,
                          int32_t q_ready, mia_stream_t stream);
 /* Byte offset in the bf16 workspace of a u32 error word: 0 after a fused backward = every dQ hand-off
  * matched; non-zero = a bounded wait gave up and that call's dQ is not valid. */
