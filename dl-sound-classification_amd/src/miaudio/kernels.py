@@ -19,6 +19,9 @@ _WS: dict = {}
 
 def workspace(nbytes: int, device, slot: str = "main") -> torch.Tensor:
     """Stream-ordered scratch buffer reused across calls (grown on demand)."""
+    # The 1.25x (+256) below is growth amortisation -- fewer reallocations while shapes still grow -- and NOT a
+    # safety margin: every kernel must stay inside the ``nbytes`` it was asked for (a C caller allocates exactly
+    # that).  tests/test_gpu_memory_contract.py replaces this function by exact, poisoned, guarded buffers.
     key = (str(device), slot)
     buf = _WS.get(key)
     nbytes = max(int(nbytes), 256)

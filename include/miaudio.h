@@ -351,7 +351,8 @@ int mia_trunk_conv8_dgrad_bn(const void* dy, const void* w, void* dx, int32_t nb
 /* Weight gradient of the EnvNet-v2 trunk conv3 (Conv2d(1, 32, (8, 8)), replaces the cuDNN backward-weight
  * of src/models/envnet_v2.py:31): dw[co][ky*8+kx] = sum dy[b][oy][ox][co] * x[b][oy+ky][ox+kx].  x bf16
  * (n, h, wd) (wd % 4 == 0, 8-byte aligned), dy bf16 (n, h-7, wd-7, 32) 16-byte aligned, dw f32 (32, 64);
- * part: f32 workspace of nwaves*2048 + 64*4096 floats, 8-byte aligned (one slab per wave, summed in fixed order). */
+ * part: f32 workspace of nwaves*2048 + 64*4096 floats, 8-byte aligned (one slab per wave, summed in fixed order);
+ * mia_conv3_wgrad_workspace_bytes(nwaves) below is that plus mia_conv3_wgrad_bn's nwaves*32 floats and covers both. */
 int mia_conv3_wgrad(const void* x, const void* dy, float* dw, float* part, int32_t nwaves, int32_t n, int32_t h,
                     int32_t wd, mia_stream_t stream);
 
