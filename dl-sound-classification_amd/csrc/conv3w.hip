@@ -11,6 +11,8 @@
 // (2 tiles): 4 MFMAs per item into 32 accumulator registers kept across all items; the next item's
 // loads are in flight while the current one computes.  dY is read from HBM exactly once; each wave
 // writes one f32 slab and a fixed-order reduce sums the slabs (bit-reproducible).
+#include <cstdlib>
+
 #include "common.h"
 
 namespace {
@@ -236,6 +238,32 @@ __global__ __launch_bounds__(256) void conv3_wgrad_reduce1_kernel(const float* _
   for (int w = w0; w < w1; ++w) s += (double)part[(int64_t)w * 2048 + e];
   tmp[gi * 2048 + e] = s;
 }
+// stage 1 with the load latency overlapped: the same groups and the same chain of f64 adds in slab order, 16 slabs
+// loaded into registers before they are added (conv3_wgrad_reduce1_kernel waits for each load before its add)
+__global__ __launch_bounds__(256) void conv3_wgrad_reduce1x16_kernel(const float* __restrict__ part, int nslab,
+                                                                     double* __restrict__ tmp) {
+  const int e = blockIdx.x * 256 + threadIdx.x, gi = blockIdx.y;
+  const int per = (nslab + C3_G - 1) / C3_G;
+  const int w0 = gi * per, w1 = min(nslab, w0 + per);
+  const float* p = part + e;
+  double s = 0.0;
+  int w = w0;
+  for (; w + 16 <= w1; w += 16) {
+    float v[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) v[u] = p[(int64_t)(w + u) * 2048];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) s += (double)v[u];
+  }
+  for (; w < w1; ++w) s += (double)p[(int64_t)w * 2048];
+  tmp[gi * 2048 + e] = s;
+}
+// A/B switch, read at call time: MIA_REDUCE_V1=1 selects conv3_wgrad_reduce1_kernel
+void conv3_wgrad_reduce1(const float* part, int nslab, double* tmp, hipStream_t s) {
+  const char* v1 = getenv("MIA_REDUCE_V1");
+  if (v1 && v1[0] == '1') conv3_wgrad_reduce1_kernel<<<dim3(8, C3_G), 256, 0, s>>>(part, nslab, tmp);
+  else conv3_wgrad_reduce1x16_kernel<<<dim3(8, C3_G), 256, 0, s>>>(part, nslab, tmp);
+}
 __global__ __launch_bounds__(256) void conv3_wgrad_reduce2_kernel(const double* __restrict__ tmp, float* __restrict__ dw) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   double s = 0.0;
@@ -260,7 +288,7 @@ extern "C" int mia_conv3_wgrad(const void* x, const void* dy, float* dw, float* 
   conv3_wgrad_kernel<false><<<nwaves / 4, 256, 0, s>>>(a);
   MIA_LAUNCH_CHECK("conv3_wgrad");
   double* tmp = reinterpret_cast<double*>(part + (int64_t)nwaves * 2048);
-  conv3_wgrad_reduce1_kernel<<<dim3(8, C3_G), 256, 0, s>>>(part, nwaves, tmp);
+  conv3_wgrad_reduce1(part, nwaves, tmp, s);
   conv3_wgrad_reduce2_kernel<<<8, 256, 0, s>>>(tmp, dw);
   MIA_LAUNCH_CHECK("conv3_wgrad_reduce");
   return 0;
@@ -291,7 +319,7 @@ extern "C" int mia_conv3_wgrad_bn(const void* x, const void* da, const void* ya,
   hipStream_t s = as_stream(stream);
   conv3_wgrad_kernel<true><<<nwaves / 4, 256, 0, s>>>(a);
   MIA_LAUNCH_CHECK("conv3_wgrad_bn");
-  conv3_wgrad_reduce1_kernel<<<dim3(8, C3_G), 256, 0, s>>>(part, nwaves, tmp);
+  conv3_wgrad_reduce1(part, nwaves, tmp, s);
   conv3_wgrad_reduce2_kernel<<<8, 256, 0, s>>>(tmp, dw);
   conv3_bias_final_kernel<<<32, 256, 0, s>>>(a.bpart, nwaves, dbias);
   MIA_LAUNCH_CHECK("conv3_wgrad_bn reduce");

@@ -1062,6 +1062,30 @@ __global__ __launch_bounds__(256) void fw_reduce_kernel(const float* __restrict_
   out[e] = acc;
 }
 
+// The same chain of adds (slab 0, 1, 2, ... into one f32 sum per element) with the latency overlapped: 64-thread
+// blocks (512 of them for the 64 x 512 gradient: every CU holds two) and 16 slabs loaded into registers before they
+// are added in slab order.  fw_reduce_kernel waits for each 4-byte load before its add on 128 blocks.
+__global__ __launch_bounds__(64) void fw_reduce16_kernel(const float* __restrict__ ws, int slabs, int len,
+                                                         float* __restrict__ out) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= len) return;
+  const float* p = ws + e;
+  float acc = 0.f;
+  int k = 0;
+  for (; k + 16 <= slabs; k += 16) {
+    float v[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) v[u] = p[(int64_t)(k + u) * len];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) acc += v[u];
+  }
+  for (; k < slabs; ++k) acc += p[(int64_t)k * len];
+  out[e] = acc;
+}
+
+// A/B switch, read at call time: MIA_REDUCE_V1=1 selects fw_reduce_kernel
+bool reduce_v1() { const char* e = getenv("MIA_REDUCE_V1"); return e && e[0] == '1'; }
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // conv2 forward form: warp-specialised unless MIA_FECONV_WS=0 (A/B runs, tools/bench_fe.py FE_AB=1)
@@ -1151,7 +1175,8 @@ extern "C" int mia_fe_conv2_wgrad(const void* dy2, const void* y1, const float* 
     MIA_LAUNCH_CHECK("fe_conv2_wgrad");
     slab0 += grid;
   }
-  fw_reduce_kernel<<<64 * 512 / 256, 256, 0, s>>>(reinterpret_cast<const float*>(workspace), slabs, 64 * 512, dw);
+  if (reduce_v1()) fw_reduce_kernel<<<64 * 512 / 256, 256, 0, s>>>(reinterpret_cast<const float*>(workspace), slabs, 64 * 512, dw);
+  else fw_reduce16_kernel<<<64 * 512 / 64, 64, 0, s>>>(reinterpret_cast<const float*>(workspace), slabs, 64 * 512, dw);
   MIA_LAUNCH_CHECK("fe_conv2_wgrad reduce");
   return 0;
 }

@@ -20,6 +20,8 @@
 //   SIMD one wave issues its MFMAs while its partner reads its fragments and issues the next
 //   LDS-DMA (MI355X_MICROARCH.md, "Two waves per SIMD"); every LDS-DMA is retired by a counted
 //   vmcnt one phase after its issue and read one barrier later;
+#include <cstdlib>
+
 #include "common.h"
 #include "gemm_common.h"
 
@@ -881,6 +883,37 @@ __global__ __launch_bounds__(256) void mg_splitk_reduce_kernel(const float* __re
   }
 }
 
+// The same chain of adds (slab 0, then 1, 2, ... into one sum per element) with the load latency overlapped: one
+// f32x4 of the output per thread on 64-thread blocks and 8 slabs loaded into registers before they are added in slab
+// order.  EnvNet's two split-K weight gradients (256 x 512 over 32 slabs, 256 x 256 over 64: 16.8 MB each) ran on
+// 128 and 64 blocks of mg_splitk_reduce_kernel, every 16-byte load waited for before its add.
+__global__ __launch_bounds__(64) void mg_splitk_reduce8_kernel(const float* __restrict__ ws, int split, int64_t M,
+                                                               int64_t N, void* out, int64_t ldc, int out_f32,
+                                                               const float* __restrict__ bias) {
+  const int64_t n4 = N >> 2;
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= M * n4) return;
+  const int64_t m = i / n4, n = (i - m * n4) * 4;
+  const float* p = ws + m * N + n;
+  const int64_t slab = M * N;
+  f32x4 s = *reinterpret_cast<const f32x4*>(p);
+  int zz = 1;
+  for (; zz + 8 <= split; zz += 8) {
+    f32x4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4*>(p + (int64_t)(zz + u) * slab);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u];
+  }
+  for (; zz < split; ++zz) s += *reinterpret_cast<const f32x4*>(p + (int64_t)zz * slab);
+  if (bias) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) s[c] += bias[n + c];
+  }
+  if (out_f32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + m * ldc + n) = s;
+  else *reinterpret_cast<uint2*>(reinterpret_cast<bf16*>(out) + m * ldc + n) = pack4(s);
+}
+
 // A-operand column sums: the split-K partials in slice order (deterministic)
 __global__ __launch_bounds__(256) void mg_acs_reduce_kernel(const float* __restrict__ part, int split, int64_t M,
                                                             float* __restrict__ out) {
@@ -1055,7 +1088,12 @@ int mg_run(const MiaOperand& A, const MiaOperand& B, const MiaEpilogue& E, int64
   if (a.split > 1) {
     const int64_t total = M * (N / 4);
     const int blocks = (int)std::min<int64_t>(cdiv(total, 256), 4096);
-    mg_splitk_reduce_kernel<<<blocks, 256, 0, s>>>(a.ws, a.split, M, N, E.ptr, E.ldc, E.dtype == MIA_F32, E.bias);
+    const char* v1 = getenv("MIA_REDUCE_V1");  // A/B switch, read at call time: the grid-stride form
+    if ((v1 && v1[0] == '1') || cdiv(total, 64) >= (1ll << 31))
+      mg_splitk_reduce_kernel<<<blocks, 256, 0, s>>>(a.ws, a.split, M, N, E.ptr, E.ldc, E.dtype == MIA_F32, E.bias);
+    else
+      mg_splitk_reduce8_kernel<<<(unsigned)cdiv(total, 64), 64, 0, s>>>(a.ws, a.split, M, N, E.ptr, E.ldc,
+                                                                         E.dtype == MIA_F32, E.bias);
     MIA_LAUNCH_CHECK("mgemm splitk reduce");
   }
   if (E.a_colsum) {

@@ -1,5 +1,7 @@
 // Small kernels of the training step: weight repacking, soft-label loss, grad-norm clip + Adam,
 // dropout, AST token assembly, on-GPU BC mixing / SpecAugment+Mixup, casts (gfx950).
+#include <cstdlib>
+
 #include "common.h"
 
 namespace {
@@ -84,7 +86,60 @@ __global__ void pack_weight_batch_kernel(PackBatch b) {
 }
 
 // ------------------------------------------------------------------ soft-label CE
-// One block; wave w handles rows w, w+4, ...
+// One row on one wave: writes the row of dlogits, returns the row's sum_c y_c log(p_c + eps) (every lane) and
+// whether the argmax of the logits is the argmax of y.
+__device__ __forceinline__ float soft_ce_row(const float* __restrict__ zr, const float* __restrict__ yr, int C,
+                                             int input_sigmoid, float invB, float* __restrict__ drow, int lane,
+                                             bool* hit) {
+  // pass 1: max of z (z = sigmoid(logit) if requested), argmax of logits and of y
+  float mx = -INFINITY, bestz = -INFINITY, besty = -INFINITY;
+  int az = 1 << 30, ay = 1 << 30;
+  for (int c = lane; c < C; c += 64) {
+    const float l = zr[c];
+    const float z = input_sigmoid ? 1.f / (1.f + __expf(-l)) : l;
+    mx = fmaxf(mx, z);
+    if (l > bestz) { bestz = l; az = c; }
+    if (yr[c] > besty) { besty = yr[c]; ay = c; }
+  }
+  mx = wave_max(mx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float bz = __shfl_xor(bestz, o, 64); const int iz = __shfl_xor(az, o, 64);
+    if (bz > bestz || (bz == bestz && iz < az)) { bestz = bz; az = iz; }
+    const float by = __shfl_xor(besty, o, 64); const int iy = __shfl_xor(ay, o, 64);
+    if (by > besty || (by == besty && iy < ay)) { besty = by; ay = iy; }
+  }
+  float se = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float l = zr[c];
+    const float z = input_sigmoid ? 1.f / (1.f + __expf(-l)) : l;
+    se += expf(z - mx);
+  }
+  se = wave_sum(se);
+  // pass 2: loss and R = sum_c y_c p_c / (p_c + eps)
+  float lrow = 0.f, R = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float l = zr[c];
+    const float z = input_sigmoid ? 1.f / (1.f + __expf(-l)) : l;
+    const float p = expf(z - mx) / se;
+    lrow += yr[c] * logf(p + 1e-8f);
+    R += yr[c] * p / (p + 1e-8f);
+  }
+  lrow = wave_sum(lrow);
+  R = wave_sum(R);
+  for (int c = lane; c < C; c += 64) {
+    const float l = zr[c];
+    const float s = input_sigmoid ? 1.f / (1.f + __expf(-l)) : l;
+    const float p = expf(s - mx) / se;
+    float g = (p * R - yr[c] * p / (p + 1e-8f)) * invB;
+    if (input_sigmoid) g *= s * (1.f - s);
+    drow[c] = g;
+  }
+  *hit = az == ay;
+  return lrow;
+}
+
+// One block; wave w handles rows w, w+16, ...  (the MIA_REDUCE_V1 form, and the form for B > CE_MAXB)
 constexpr int CE_NT = 1024;
 __global__ __launch_bounds__(CE_NT) void soft_ce_kernel(const float* __restrict__ logits, const float* __restrict__ y,
                                                         int B, int C, int input_sigmoid, float* loss_out,
@@ -96,53 +151,58 @@ __global__ __launch_bounds__(CE_NT) void soft_ce_kernel(const float* __restrict_
   int hits = 0;
   const float invB = 1.f / (float)B;
   for (int b = wave; b < B; b += CE_NT / 64) {
-    const float* zr = logits + (int64_t)b * C;
-    const float* yr = y + (int64_t)b * C;
-    // pass 1: max of z (z = sigmoid(logit) if requested), argmax of logits and of y
-    float mx = -INFINITY, bestz = -INFINITY, besty = -INFINITY;
-    int az = 1 << 30, ay = 1 << 30;
-    for (int c = lane; c < C; c += 64) {
-      const float l = zr[c];
-      const float z = input_sigmoid ? 1.f / (1.f + __expf(-l)) : l;
-      mx = fmaxf(mx, z);
-      if (l > bestz) { bestz = l; az = c; }
-      if (yr[c] > besty) { besty = yr[c]; ay = c; }
+    bool hit;
+    const float lrow = soft_ce_row(logits + (int64_t)b * C, y + (int64_t)b * C, C, input_sigmoid, invB,
+                                   dlogits + (int64_t)b * C, lane, &hit);
+    if (lane == 0) { lsum += -(double)lrow; hits += hit; }
+  }
+  if (lane == 0) { wl[wave] = lsum; wc[wave] = hits; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tl = 0.0;
+    int tc = 0;
+    for (int w = 0; w < CE_NT / 64; ++w) { tl += wl[w]; tc += wc[w]; }
+    loss_out[0] = (float)(tl / (double)B);
+    if (correct_out) correct_out[0] = tc;
+  }
+}
+
+// The same rows spread over the chip: one wave per row (four rows per block) writes dlogits and leaves the row's
+// -lrow (double) and hit flag in a per-device scratch; soft_ce_final_kernel then forms the loss and the count in
+// soft_ce_kernel's order -- wave w adds rows w, w+16, ... in row order, the 16 wave sums are added in wave order --
+// so loss, dlogits and correct are bit for bit those of the one-block form, which walked its 16 rows per wave (four
+// dependent passes each) while 255 CUs idled.  mia_soft_ce has no workspace argument, so the scratch is the
+// library's: like the cached workspace() buffers of kernels.py it is shared by every call on a device, and calls
+// on one device must be ordered by their streams (they are: the step runs on one stream).
+constexpr int CE_MAXB = 8192;
+__device__ double ce_row_loss[CE_MAXB];
+__device__ int ce_row_hit[CE_MAXB];
+__global__ __launch_bounds__(256) void soft_ce_rows_kernel(const float* __restrict__ logits, const float* __restrict__ y,
+                                                           int B, int C, int input_sigmoid,
+                                                           float* __restrict__ dlogits) {
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  bool hit;
+  const float lrow = soft_ce_row(logits + (int64_t)b * C, y + (int64_t)b * C, C, input_sigmoid, 1.f / (float)B,
+                                 dlogits + (int64_t)b * C, lane, &hit);
+  if (lane == 0) { ce_row_loss[b] = -(double)lrow; ce_row_hit[b] = hit; }
+}
+__global__ __launch_bounds__(CE_NT) void soft_ce_final_kernel(int B, float* loss_out, int* correct_out) {
+  __shared__ double wl[CE_NT / 64];
+  __shared__ int wc[CE_NT / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double lsum = 0.0;
+  int hits = 0;
+  // lane j holds row wave + 16 (b0 + j): 64 loads in flight, then added by lane 0's chain in row order
+  for (int b0 = 0; wave + 16 * b0 < B; b0 += 64) {
+    const int b = wave + 16 * (b0 + lane);
+    const double v = b < B ? ce_row_loss[b] : 0.0;
+    const int h = b < B ? ce_row_hit[b] : 0;
+    const int nrow = min(64, (B - wave - 16 * b0 + 15) / 16);
+    for (int j = 0; j < nrow; ++j) {
+      lsum += __shfl(v, j, 64);
+      hits += __shfl(h, j, 64);
     }
-    mx = wave_max(mx);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float bz = __shfl_xor(bestz, o, 64); const int iz = __shfl_xor(az, o, 64);
-      if (bz > bestz || (bz == bestz && iz < az)) { bestz = bz; az = iz; }
-      const float by = __shfl_xor(besty, o, 64); const int iy = __shfl_xor(ay, o, 64);
-      if (by > besty || (by == besty && iy < ay)) { besty = by; ay = iy; }
-    }
-    float se = 0.f;
-    for (int c = lane; c < C; c += 64) {
-      const float l = zr[c];
-      const float z = input_sigmoid ? 1.f / (1.f + __expf(-l)) : l;
-      se += expf(z - mx);
-    }
-    se = wave_sum(se);
-    // pass 2: loss and R = sum_c y_c p_c / (p_c + eps)
-    float lrow = 0.f, R = 0.f;
-    for (int c = lane; c < C; c += 64) {
-      const float l = zr[c];
-      const float z = input_sigmoid ? 1.f / (1.f + __expf(-l)) : l;
-      const float p = expf(z - mx) / se;
-      lrow += yr[c] * logf(p + 1e-8f);
-      R += yr[c] * p / (p + 1e-8f);
-    }
-    lrow = wave_sum(lrow);
-    R = wave_sum(R);
-    for (int c = lane; c < C; c += 64) {
-      const float l = zr[c];
-      const float s = input_sigmoid ? 1.f / (1.f + __expf(-l)) : l;
-      const float p = expf(s - mx) / se;
-      float g = (p * R - yr[c] * p / (p + 1e-8f)) * invB;
-      if (input_sigmoid) g *= s * (1.f - s);
-      dlogits[(int64_t)b * C + c] = g;
-    }
-    if (lane == 0) { lsum += -(double)lrow; hits += (az == ay); }
   }
   if (lane == 0) { wl[wave] = lsum; wc[wave] = hits; }
   __syncthreads();
@@ -658,7 +718,13 @@ extern "C" int mia_pack_weights(const MiaPackJob* jobs, int32_t n, mia_stream_t 
 extern "C" int mia_soft_ce(const float* logits, const float* y, int32_t B, int32_t C, int32_t input_sigmoid, float* loss,
                            float* dlogits, int32_t* correct, mia_stream_t stream) {
   MIA_CHECK_ARG(logits && y && loss && dlogits && B > 0 && C > 0, "soft_ce: args");
-  soft_ce_kernel<<<1, CE_NT, 0, as_stream(stream)>>>(logits, y, B, C, input_sigmoid, loss, dlogits, correct);
+  const char* v1 = getenv("MIA_REDUCE_V1");  // A/B switch, read at call time: the one-block form
+  if ((v1 && v1[0] == '1') || B > CE_MAXB) {
+    soft_ce_kernel<<<1, CE_NT, 0, as_stream(stream)>>>(logits, y, B, C, input_sigmoid, loss, dlogits, correct);
+  } else {
+    soft_ce_rows_kernel<<<(unsigned)cdiv(B, 4), 256, 0, as_stream(stream)>>>(logits, y, B, C, input_sigmoid, dlogits);
+    soft_ce_final_kernel<<<1, CE_NT, 0, as_stream(stream)>>>(B, loss, correct);
+  }
   MIA_LAUNCH_CHECK("soft_ce");
   return 0;
 }

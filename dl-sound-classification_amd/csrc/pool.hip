@@ -31,11 +31,76 @@ __device__ __forceinline__ int64_t out_index(int layout, int b, int oy, int ox, 
   return (((int64_t)b * C + c) * OH + oy) * OW + ox;                       // NCHW flat
 }
 
-// one thread = one (output pixel, 8-channel group)
+// A/B switch, read at call time: MIA_POOL_V1=1 selects the earlier forms of pool_fwd (run-time window walk,
+// per-element transposed stores) and of pool_bwd_gather (per-element gathers of the pooled gradient)
+bool pool_v1() { const char* e = getenv("MIA_POOL_V1"); return e && e[0] == '1'; }
+
+// Block ids are dealt round-robin to the 8 XCDs (each with its own L2), so neighbouring blocks that touch the same
+// 128-B lines of a channel-major tensor would each fetch them into a different L2.  This bijective relabelling
+// gives every group of blocks that share an XCD a contiguous range of logical ids; what a logical block computes
+// does not depend on where it runs, so results are unchanged.
+__device__ __forceinline__ int xcd_block_id() {
+  const int nwg = gridDim.x, q = nwg / 8, r = nwg % 8, x = blockIdx.x % 8;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + blockIdx.x / 8;
+}
+
+// The window of one (pooled cell, 8-channel group): best = max relu(sc * x + sh), raw = the winner's x, arg its
+// position; row-major window order, the first maximum wins (torch's tie rule).  off0 = the element offset of the
+// window's first pixel for this group.  KH, KW > 0: a compile-time window (EnvNet's (1, 2) and (5, 3)) -- the
+// loops unroll and every load is issued before the first compare; KH == 0: the run-time window (kh, kw).
+template <int KH, int KW>
+__device__ __forceinline__ void pool_window_dt(const void* __restrict__ x, int dtype, int64_t off0, int W, int C,
+                                               int kh, int kw, const float (&sc)[8], const float (&sh)[8],
+                                               float (&best)[8], float (&raw)[8], int (&arg)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { best[i] = -INFINITY; raw[i] = 0.f; arg[i] = 0; }
+  if constexpr (KH > 0) {
+    float f[KH * KW][8];
+#pragma unroll
+    for (int dy = 0; dy < KH; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < KW; ++dx) load8(x, dtype, off0 + ((int64_t)dy * W + dx) * C, f[dy * KW + dx]);
+#pragma unroll
+    for (int pos = 0; pos < KH * KW; ++pos)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float v = fmaxf(fmaf(f[pos][i], sc[i], sh[i]), 0.f);
+        if (v > best[i]) { best[i] = v; raw[i] = f[pos][i]; arg[i] = pos; }
+      }
+  } else {
+    for (int dy = 0; dy < kh; ++dy) {
+      for (int dx = 0; dx < kw; ++dx) {
+        float f[8];
+        load8(x, dtype, off0 + ((int64_t)dy * W + dx) * C, f);
+        const int pos = dy * kw + dx;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float v = fmaxf(fmaf(f[i], sc[i], sh[i]), 0.f);
+          if (v > best[i]) { best[i] = v; raw[i] = f[i]; arg[i] = pos; }
+        }
+      }
+    }
+  }
+}
+
+template <int KH, int KW>
+__device__ __forceinline__ void pool_window(const void* __restrict__ x, int dtype, int64_t off0, int W, int C, int kh,
+                                            int kw, const float (&sc)[8], const float (&sh)[8], float (&best)[8],
+                                            float (&raw)[8], int (&arg)[8]) {
+  // the dtype as a constant in each arm: no branch between the unrolled loads.  An f32 window of more than 4 pixels
+  // walks (its 8 registers a pixel would set the kernel's register count; f32 is not the training step's dtype).
+  if (dtype == MIA_BF16) pool_window_dt<KH, KW>(x, MIA_BF16, off0, W, C, kh, kw, sc, sh, best, raw, arg);
+  else if constexpr (KH * KW <= 4) pool_window_dt<KH, KW>(x, MIA_F32, off0, W, C, kh, kw, sc, sh, best, raw, arg);
+  else pool_window_dt<0, 0>(x, MIA_F32, off0, W, C, kh, kw, sc, sh, best, raw, arg);
+}
+
+// one thread = one (output pixel, 8-channel group); <0, 0> is the run-time window (and the MIA_POOL_V1 form)
+template <int KH, int KW>
 __global__ __launch_bounds__(NT) void pool_fwd_kernel(const void* __restrict__ x, int dtype, int n, int H, int W,
                                                       int C, int kh, int kw, const float* __restrict__ scale,
                                                       const float* __restrict__ shift, void* out, int layout,
                                                       uint8_t* __restrict__ argmax, void* __restrict__ win) {
+  if constexpr (KH > 0) { kh = KH; kw = KW; }
   const int OH = H / kh, OW = W / kw, G = C / 8;
   const int total = n * OH * OW * G;  // < 2^31 (checked by the launcher): 32-bit index math
   for (int idx = blockIdx.x * NT + threadIdx.x; idx < total; idx += gridDim.x * NT) {
@@ -51,34 +116,9 @@ __global__ __launch_bounds__(NT) void pool_fwd_kernel(const void* __restrict__ x
     for (int i = 0; i < 8; ++i) {
       sc[i] = scale ? scale[cg * 8 + i] : 1.f;
       sh[i] = shift ? shift[cg * 8 + i] : 0.f;
-      best[i] = -INFINITY;
-      raw[i] = 0.f;
-      arg[i] = 0;
     }
-    for (int dy = 0; dy < kh; ++dy) {
-      const int iy = oy * kh + dy;
-      for (int dx = 0; dx < kw; ++dx) {
-        const int ix = ox * kw + dx;
-        const int64_t off = (((int64_t)b * H + iy) * W + ix) * C + cg * 8;
-        float f[8];
-        if (dtype == MIA_BF16) {
-          uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(x) + off);
-          uint32_t w4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w4[i] << 16); f[2 * i + 1] = __uint_as_float(w4[i] & 0xffff0000u); }
-        } else {
-          const float4* q = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(x) + off);
-          float4 a = q[0], c4 = q[1];
-          f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = c4.x; f[5] = c4.y; f[6] = c4.z; f[7] = c4.w;
-        }
-        const int pos = dy * kw + dx;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float v = fmaxf(fmaf(f[i], sc[i], sh[i]), 0.f);
-          if (v > best[i]) { best[i] = v; raw[i] = f[i]; arg[i] = pos; }
-        }
-      }
-    }
+    pool_window<KH, KW>(x, dtype, (((int64_t)b * H + oy * kh) * W + ox * kw) * C + cg * 8, W, C, kh, kw, sc, sh, best,
+                        raw, arg);
     const int64_t aoff = (((int64_t)b * OH + oy) * OW + ox) * C + cg * 8;
     uint32_t a0 = 0, a1 = 0;
 #pragma unroll
@@ -90,6 +130,90 @@ __global__ __launch_bounds__(NT) void pool_fwd_kernel(const void* __restrict__ x
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) st_elem(out, dtype, out_index(layout, b, oy, ox, cg * 8 + i, OH, OW, C), best[i]);
+    }
+  }
+}
+
+// pool_fwd into a channel-major output (layouts 1 and 2: out[(b * C + c) * S + p], S = OH * OW, p = oy * OW + ox):
+// a block owns 64 consecutive cells p of one image x 64 channels.  The windows are walked as in pool_fwd_kernel
+// (argmax and win go out as contiguous NHWC runs), the pooled values are rounded to the output dtype into a padded
+// LDS tile [channel][cell] and written back as runs along p -- bf16: 8-B stores of 4 cells, started at the row's
+// first 8-byte boundary, the ragged ends element by element; f32: one element per lane, 256 B per wave -- like
+// pool_apply_t64_kernel (the per-element form scattered 2-B stores S * 2 bytes apart).  Same arithmetic, same bits.
+constexpr int PT = 64;  // cells and channels per tile
+template <int KH, int KW>
+__global__ __launch_bounds__(NT) void pool_fwd_tr_kernel(const void* __restrict__ x, int dtype, int H, int W, int C,
+                                                         int kh, int kw, const float* __restrict__ scale,
+                                                         const float* __restrict__ shift, void* out,
+                                                         uint8_t* __restrict__ argmax, void* __restrict__ win) {
+  if constexpr (KH > 0) { kh = KH; kw = KW; }
+  __shared__ __attribute__((aligned(16))) float tile_raw[PT * (PT + 1)];
+  float(*tf)[PT + 1] = reinterpret_cast<float(*)[PT + 1]>(tile_raw);  // f32: [channel][cell]
+  bf16(*tb)[PT + 4] = reinterpret_cast<bf16(*)[PT + 4]>(tile_raw);    // bf16: [channel][cell]
+  const int OW = W / kw, S = (H / kh) * OW, G = C / 8;
+  const int chunks = (C + PT - 1) / PT, tiles = (S + PT - 1) / PT;
+  int bi = xcd_block_id();  // tiles that are neighbours along p (they share output lines) on one L2
+  const int chunk = bi % chunks;
+  bi /= chunks;
+  const int b = bi / tiles, p0 = (bi - b * tiles) * PT;
+  const int np = min(PT, S - p0);
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < PT * PT / 8 / NT; ++k) {
+    const int q = t + NT * k, r = q >> 3, ch = q & 7;  // cell p0 + r, channels 8 cg .. 8 cg + 7
+    const int cg = chunk * (PT / 8) + ch;
+    if (r >= np || cg >= G) continue;
+    const int p = p0 + r, oy = p / OW, ox = p - oy * OW;
+    float sc[8], sh[8], best[8], raw[8];
+    int arg[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      sc[i] = scale ? scale[cg * 8 + i] : 1.f;
+      sh[i] = shift ? shift[cg * 8 + i] : 0.f;
+    }
+    pool_window<KH, KW>(x, dtype, (((int64_t)b * H + oy * kh) * W + ox * kw) * C + cg * 8, W, C, kh, kw, sc, sh, best,
+                        raw, arg);
+    const int64_t aoff = ((int64_t)b * S + p) * C + cg * 8;
+    uint32_t a0 = 0, a1 = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { a0 |= (uint32_t)arg[i] << (8 * i); a1 |= (uint32_t)arg[i + 4] << (8 * i); }
+    *reinterpret_cast<uint2*>(argmax + aoff) = make_uint2(a0, a1);
+    if (win) store8(win, dtype, aoff, raw);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (dtype == MIA_BF16) tb[ch * 8 + i][r] = (bf16)best[i];
+      else tf[ch * 8 + i][r] = best[i];
+    }
+  }
+  __syncthreads();
+  const int nc = min(PT, C - chunk * PT);
+  const int64_t row0 = ((int64_t)b * C + chunk * PT) * S + p0;  // out element of (channel 0 of the chunk, cell p0)
+  if (dtype == MIA_BF16) {
+    bf16* o = reinterpret_cast<bf16*>(out) + row0;
+    constexpr int NJ = PT / 4 + 1;  // 4-cell pieces per row, the first one starting up to 3 cells early
+    for (int q = t; q < PT * NJ; q += NT) {
+      const int c = q / NJ, j = q - c * NJ;
+      if (c >= nc) break;
+      bf16* dst = o + (int64_t)c * S;
+      const int lead = (int)((reinterpret_cast<uintptr_t>(dst) >> 1) & 3);  // cells past an 8-byte boundary
+      const int lo = 4 * j - lead;
+      if (lo >= 0 && lo + 4 <= np) {
+        bf16x4 w4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w4[i] = tb[c][lo + i];
+        *reinterpret_cast<bf16x4*>(dst + lo) = w4;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (lo + i >= 0 && lo + i < np) dst[lo + i] = tb[c][lo + i];
+      }
+    }
+  } else {
+    float* o = reinterpret_cast<float*>(out) + row0;
+    for (int q = t; q < PT * PT; q += NT) {
+      const int c = q >> 6, r = q & (PT - 1);
+      if (c >= nc) break;
+      if (r < np) o[(int64_t)c * S + r] = tf[c][r];
     }
   }
 }
@@ -382,6 +506,123 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_kernel(const void* __restr
     float acc = 0.f;
     for (int r2 = 0; r2 < rslots; ++r2) acc += red[(r2 * G + g2) * 16 + qq * 8 + ci];
     partial[((int64_t)blockIdx.x * C + c) * 2 + qq] = acc;
+  }
+}
+
+// pool_bwd_sparse_kernel for a channel-major pooled gradient (layouts 1 and 2: dout[(b * C + c) * S + p],
+// S = OH * OW) with the winners saved (win): same grid, same cell -> (block, thread) map, same per-thread sums and
+// in-block combine, so gm and partial come out bit for bit.  Only the way dout arrives changes: the block's
+// rslots consecutive cells x C channels are staged through LDS -- per channel a run of cells that is contiguous
+// in memory, read in 4-cell pieces (8 B bf16 / 16 B f32) where the piece is aligned and stays in one image, cell
+// by cell at the ragged ends -- instead of eight 2-byte loads from eight cache lines per thread and cell.  The next
+// iteration's dout pieces and win row are requested before this iteration's arithmetic.  rslots % 4 == 0 (the
+// launcher takes this form from rslots = 16 on).
+__global__ __launch_bounds__(NT) void pool_bwd_sparse_tr_kernel(const void* __restrict__ dout,
+                                                                const uint8_t* __restrict__ argmax,
+                                                                const void* __restrict__ x,
+                                                                const void* __restrict__ win, int dtype, int cells,
+                                                                int H, int W, int C, int kh, int kw, int lg_nch,
+                                                                const float* __restrict__ scale,
+                                                                const float* __restrict__ shift,
+                                                                const float* __restrict__ mean,
+                                                                const float* __restrict__ invstd,
+                                                                float* __restrict__ gm, float* __restrict__ partial) {
+  const int OW = W / kw, S = (H / kh) * OW, G = C / 8;
+  const int t = threadIdx.x;
+  const int lb = xcd_block_id();  // the logical block: blocks whose cells share dout lines on one L2
+  const int cg = t % G, rs = t / G, rslots = NT / G;
+  const int LD = C + 4;  // tile row (one cell) in floats: 16-B aligned rows
+  __shared__ __attribute__((aligned(16))) float red[NT * 16];  // the dout tile [rslots][LD] until the final combine
+  float* tile = red;
+  float sc[8], sh[8], mu[8], is[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    sc[i] = scale[cg * 8 + i]; sh[i] = shift[cg * 8 + i]; mu[i] = mean[cg * 8 + i]; is[i] = invstd[cg * 8 + i];
+  }
+  float s1[8] = {0}, s2[8] = {0};
+  const int es = dtype == MIA_BF16 ? 1 : 2;
+  const uintptr_t dbase = reinterpret_cast<uintptr_t>(dout) >> es;  // dout's address in elements
+  // piece u of this thread: channel pc[u], cells 4 pk[u] .. + 3 of the block's rslots (C * rslots / 4 = 512 pieces)
+  int pc[2], pk[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) { const int q = t + NT * u; pc[u] = q >> lg_nch; pk[u] = q & ((1 << lg_nch) - 1); }
+  float pv[2][4], wx[8] = {0};
+  auto fetch = [&](int cell0) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int c0 = cell0 + 4 * pk[u];
+      const int b0 = c0 / S, b3 = (c0 + 3) / S;
+      const int64_t i0 = ((int64_t)b0 * C + pc[u]) * S + (c0 - b0 * S);
+      if (c0 + 3 < cells && b0 == b3 && ((dbase + (uintptr_t)i0) & 3) == 0) {
+        if (dtype == MIA_BF16) {
+          const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16*>(dout) + i0);
+          pv[u][0] = __uint_as_float(v.x << 16); pv[u][1] = __uint_as_float(v.x & 0xffff0000u);
+          pv[u][2] = __uint_as_float(v.y << 16); pv[u][3] = __uint_as_float(v.y & 0xffff0000u);
+        } else {
+          const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(dout) + i0);
+          pv[u][0] = v.x; pv[u][1] = v.y; pv[u][2] = v.z; pv[u][3] = v.w;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int cj = c0 + j, bj = cj / S;
+          pv[u][j] = cj < cells ? ld_elem(dout, dtype, ((int64_t)bj * C + pc[u]) * S + (cj - bj * S)) : 0.f;
+        }
+      }
+    }
+    if (win && cell0 + rs < cells) load8(win, dtype, (int64_t)(cell0 + rs) * C + cg * 8, wx);
+  };
+  const int64_t step = (int64_t)gridDim.x * rslots;
+  int64_t cell0 = (int64_t)lb * rslots;
+  if (cell0 < cells) fetch((int)cell0);
+  for (; cell0 < cells; cell0 += step) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tile[(4 * pk[u] + j) * LD + pc[u]] = pv[u][j];
+    float xv[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) xv[i] = wx[i];
+    __syncthreads();
+    if (cell0 + step < cells) fetch((int)(cell0 + step));
+    const int64_t cell = cell0 + rs;
+    if (cell < cells) {
+      const float4 d0 = *reinterpret_cast<const float4*>(tile + rs * LD + cg * 8);
+      const float4 d1 = *reinterpret_cast<const float4*>(tile + rs * LD + cg * 8 + 4);
+      const float dv[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+      if (!win) {  // no saved winners: gather x at the argmax positions, as pool_bwd_sparse_kernel does
+        const int b = (int)cell / S, p = (int)cell - b * S, oy = p / OW, ox = p - oy * OW;
+        const uint2 am = *reinterpret_cast<const uint2*>(argmax + cell * C + cg * 8);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const uint32_t word = i < 4 ? am.x : am.y;
+          const int a = (int)((word >> (8 * (i & 3))) & 0xffu);
+          const int iy = oy * kh + a / kw, ix = ox * kw + a % kw;
+          xv[i] = ld_elem(x, dtype, (((int64_t)b * H + iy) * W + ix) * C + cg * 8 + i);
+        }
+      }
+      float gv[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float g = fmaf(xv[i], sc[i], sh[i]) > 0.f ? dv[i] : 0.f;
+        gv[i] = g;
+        s1[i] += g;
+        s2[i] = fmaf(g, (xv[i] - mu[i]) * is[i], s2[i]);
+      }
+      float4* gq = reinterpret_cast<float4*>(gm + cell * C + cg * 8);
+      gq[0] = make_float4(gv[0], gv[1], gv[2], gv[3]);
+      gq[1] = make_float4(gv[4], gv[5], gv[6], gv[7]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { red[t * 16 + i] = s1[i]; red[t * 16 + 8 + i] = s2[i]; }
+  __syncthreads();
+  for (int e = t; e < 2 * C; e += NT) {
+    const int qq = e / C, c = e % C, g2 = c / 8, ci = c % 8;
+    float acc = 0.f;
+    for (int r2 = 0; r2 < rslots; ++r2) acc += red[(r2 * G + g2) * 16 + qq * 8 + ci];
+    partial[((int64_t)lb * C + c) * 2 + qq] = acc;
   }
 }
 
@@ -712,8 +953,26 @@ extern "C" int mia_pool_fwd(const void* x, int32_t dtype, int32_t n, int32_t h, 
   MIA_CHECK_ARG((int64_t)n * h * w * (c / 8) < (1ll << 31), "pool_fwd: too many elements for 32-bit indexing");
   const int64_t total = (int64_t)n * (h / kh) * (w / kw) * (c / 8);
   const int nb = (int)std::min<int64_t>(cdiv(total, NT), 16384);
-  pool_fwd_kernel<<<nb, NT, 0, as_stream(stream)>>>(x, dtype, n, h, w, c, kh, kw, scale, shift, out, out_layout, argmax,
-                                                    win);
+  hipStream_t s = as_stream(stream);
+  const bool v1 = pool_v1();
+  const int win_id = v1 ? 0 : (kh == 1 && kw == 2) ? 1 : (kh == 5 && kw == 3) ? 2 : 0;  // the windows EnvNet uses
+  const int64_t tblocks = (int64_t)n * cdiv((int64_t)(h / kh) * (w / kw), PT) * cdiv(c, PT);
+  if (!v1 && out_layout != 0 && tblocks < (1ll << 31)) {  // channel-major output: through an LDS transpose
+    if (win_id == 1)
+      pool_fwd_tr_kernel<1, 2><<<(unsigned)tblocks, NT, 0, s>>>(x, dtype, h, w, c, kh, kw, scale, shift, out, argmax, win);
+    else if (win_id == 2)
+      pool_fwd_tr_kernel<5, 3><<<(unsigned)tblocks, NT, 0, s>>>(x, dtype, h, w, c, kh, kw, scale, shift, out, argmax, win);
+    else
+      pool_fwd_tr_kernel<0, 0><<<(unsigned)tblocks, NT, 0, s>>>(x, dtype, h, w, c, kh, kw, scale, shift, out, argmax, win);
+    MIA_LAUNCH_CHECK("pool_fwd_tr");
+    return 0;
+  }
+  // NHWC output: the (1, 2) window measured no faster unrolled (EnvNet's two: 53.4 -> 51.7 and 87.9 -> 86.3 us) and
+  // stays on the run-time walk; (5, 3) went 176 -> 157 us
+  if (win_id == 2)
+    pool_fwd_kernel<5, 3><<<nb, NT, 0, s>>>(x, dtype, n, h, w, c, kh, kw, scale, shift, out, out_layout, argmax, win);
+  else
+    pool_fwd_kernel<0, 0><<<nb, NT, 0, s>>>(x, dtype, n, h, w, c, kh, kw, scale, shift, out, out_layout, argmax, win);
   MIA_LAUNCH_CHECK("pool_fwd");
   return 0;
 }
@@ -788,8 +1047,18 @@ extern "C" int mia_pool_bwd_gather(const void* dout, int32_t out_layout, const u
   const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(cells, (int64_t)rslots * 2), 1024));
   hipStream_t s = as_stream(stream);
   MIA_CHECK_ARG(!win || (reinterpret_cast<uintptr_t>(win) & 15) == 0, "pool_bwd_gather: win alignment");
-  pool_bwd_sparse_kernel<<<nb, NT, 0, s>>>(dout, out_layout, argmax, x, win, dtype, n, h, w, c, kh, kw, scale, shift, mean,
-                                           invstd, gm, (float*)partial);
+  // the staged form from 16 cells a block iteration on (channel runs of 32 B and more; C <= 128): the frontend's
+  // gradient (C = 64) went 50 -> 33 us, the last trunk pool's (C = 256, 8 cells, 16-B runs) measured 87 -> 89 us
+  if (!pool_v1() && (out_layout == 2 || (out_layout == 1 && h / kh == 1)) && rslots >= 16 &&
+      cells < (1ll << 31) - 1024) {
+    int lg_nch = 0;
+    while ((4 << lg_nch) < rslots) ++lg_nch;  // rslots / 4 pieces per channel (rslots divides 256: a power of two)
+    pool_bwd_sparse_tr_kernel<<<nb, NT, 0, s>>>(dout, argmax, x, win, dtype, (int)cells, h, w, c, kh, kw, lg_nch, scale,
+                                                shift, mean, invstd, gm, (float*)partial);
+  } else {
+    pool_bwd_sparse_kernel<<<nb, NT, 0, s>>>(dout, out_layout, argmax, x, win, dtype, n, h, w, c, kh, kw, scale, shift,
+                                             mean, invstd, gm, (float*)partial);
+  }
   MIA_LAUNCH_CHECK("pool_bwd_gather");
   partial_final_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, dgamma, dbeta);
   MIA_LAUNCH_CHECK("pool_bwd_gather_final");
