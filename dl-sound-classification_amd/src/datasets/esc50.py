@@ -10,6 +10,10 @@ onto the GPU:
   training-set pool (EnvNet) or the batched HIP log-mel -> SpecAugment -> Mixup against the
   resident un-augmented spectrogram pool (AST).  Labels become the same soft (B, C) f32 targets the
   reference produces, so LitClassifier's soft-label loss branch runs as in the reference.
+* When ``preprocessing_config.sample_rate`` differs from the data module's ``sample_rate`` the clips are
+  resampled first, as the reference's preprocessors do (preprocessing.py:822, :1021): once, on the GPU, in
+  ``setup()`` (``resample.build_store``); window, padding and the log-mel filter bank are then in target-rate
+  terms.  With equal rates (the default: the target falls back to the data module's rate) nothing changes.
 ``SyntheticDataModule`` serves device-resident synthetic clips (benchmarks, plumbing runs).
 """
 from __future__ import annotations
@@ -36,7 +40,11 @@ def _one_hot(y: torch.Tensor, C: int) -> torch.Tensor:
 class ESC50Dataset(Dataset):
     def __init__(self, root, folds: Sequence[int] = (), files: List[Path] | None = None, mode: str = "envnet_v2",
                  pad_crop: bool = False, window_length: float = 5.0, padding_ratio: float = 0.5,
-                 training: bool = True, multi_crop_test: bool = False, test_crops: int = 10):
+                 training: bool = True, multi_crop_test: bool = False, test_crops: int = 10,
+                 sample_rate: int = SR, store=None):
+        """``sample_rate``: the rate the window and the padding are counted in.  ``store``: a
+        ``resample.ResampledStore`` that already holds every clip at that rate; ``load`` then reads from it
+        instead of the bundle."""
         self.root = Path(root)
         if files is not None:
             self.files = list(files)
@@ -47,7 +55,8 @@ class ESC50Dataset(Dataset):
         if not self.files:
             raise FileNotFoundError(f"No .pt files found in {self.root}; did you run scripts/prepare_esc50.py?")
         self.mode, self.pad_crop, self.training = mode, pad_crop, training
-        self.window = int(window_length * SR)
+        self.window = int(window_length * sample_rate)
+        self.store = store
         self.pad = int(self.window * padding_ratio)
         self.multi_crop_test, self.test_crops = multi_crop_test, test_crops
 
@@ -55,6 +64,8 @@ class ESC50Dataset(Dataset):
         return len(self.files)
 
     def load(self, idx):
+        if self.store is not None:
+            return self.store.get(self.files[idx])
         b = torch.load(self.files[idx], map_location="cpu", weights_only=True)
         return b["waveform"].float().reshape(1, -1), int(b["label"])
 
@@ -123,6 +134,14 @@ class ESC50DataModule:
         self._pool = self._pool_labels = None
         self._logmel = None
         self._gen = None
+        self._store = None
+
+    @property
+    def target_rate(self) -> int:
+        """The rate the preprocessor works at (reference EnvNetPreprocessor / ASTPreprocessor ``sample_rate``).
+        Defaults to the data module's own rate, not to the reference's 44100: every configuration that names no
+        preprocessing_config.sample_rate stays on the path without resampling."""
+        return int(self.preprocessing_config.get("sample_rate", self.sample_rate))
 
     @classmethod
     def _fold_error(cls) -> str:
@@ -156,6 +175,8 @@ class ESC50DataModule:
 
     def _ds(self, **kw):
         pc = self.preprocessing_config
+        if self.target_rate != self.sample_rate:  # window and padding in target-rate samples, clips from the store
+            kw = dict(kw, sample_rate=self.target_rate, store=self._store)
         return ESC50Dataset(self.root, mode=self.preprocessing_mode,
                             window_length=pc.get("window_length", 5.0), padding_ratio=pc.get("padding_ratio", 0.5),
                             multi_crop_test=pc.get("multi_crop_test", False), test_crops=pc.get("test_crops", 10), **kw)
@@ -165,6 +186,12 @@ class ESC50DataModule:
             return
         from sklearn.model_selection import StratifiedShuffleSplit
         train_folds = [f for f in range(self.NUM_FOLDS) if f != self.fold]
+        if self.target_rate != self.sample_rate:
+            # the reference's order (preprocessing.py:822, :1021): resample the whole clip first, then pad and crop
+            # in target-rate samples.  One pass over every file; the three datasets read the result.
+            from .resample import build_store
+            every = ESC50Dataset(self.root, folds=list(range(self.NUM_FOLDS))).files
+            self._store = build_store(every, self.sample_rate, self.target_rate, self.device)
         full = self._ds(folds=train_folds, training=True)
         labels = [full.load(i)[1] for i in range(len(full))]
         val_size = math.ceil(len(full) * self.val_split)
@@ -200,7 +227,7 @@ class ESC50DataModule:
         if self._logmel is None:
             from .features import GpuLogMel
             pc = self.preprocessing_config
-            self._logmel = GpuLogMel(self.sample_rate, pc.get("n_mels", self.n_mels), pc.get("normalize", True),
+            self._logmel = GpuLogMel(self.target_rate, pc.get("n_mels", self.n_mels), pc.get("normalize", True),
                                      pc.get("target_mean", 0.0), pc.get("target_std", 0.5))
         return self._logmel
 
@@ -307,6 +334,14 @@ class SyntheticDataModule(ESC50DataModule):
         g = torch.Generator(device=self.device).manual_seed(self.seed)
         x = 0.1 * torch.randn(self.num_clips, 1, self.clip_samples, generator=g, device=self.device)
         x = x / x.abs().amax(dim=-1, keepdim=True)
+        if self.target_rate != self.sample_rate:  # clips are generated at the data module's rate
+            if self.device.type != "cuda":
+                raise ValueError(f"sample_rate={self.sample_rate} differs from preprocessing_config.sample_rate="
+                                 f"{self.target_rate}: resampling runs on the GPU (there is no CPU resampler), but "
+                                 f"the device is {self.device}")
+            from .resample import MAX_CLIPS_PER_LAUNCH, GpuResample
+            rs = GpuResample(self.sample_rate, self.target_rate)
+            x = torch.cat([rs(x[i:i + MAX_CLIPS_PER_LAUNCH]) for i in range(0, x.shape[0], MAX_CLIPS_PER_LAUNCH)])
         y = torch.randint(0, self.num_classes, (self.num_clips,), generator=g, device=self.device)
         n = self.num_clips
         nv = max(1, n // 10)

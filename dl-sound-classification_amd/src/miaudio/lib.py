@@ -173,6 +173,9 @@ SIGNATURES = {
     "mia_lt_pool_bwd_apply": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mia_lt_pcen_fwd": (C.c_int, [vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, vp]),
     "mia_lt_pcen_bwd": (C.c_int, [vp, vp, vp, f32, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    # include/miaudio_resample.h
+    "mia_resample_out_len": (i64, [i64, i32, i32]),
+    "mia_resample": (C.c_int, [vp, i64, i32, i64, vp, vp, i32, i32, i32, vp, i64, i64, vp]),
     "mia_last_error_string": (C.c_char_p, []),
     "mia_device_arch": (C.c_int, [C.c_char_p, i32]),
 }
