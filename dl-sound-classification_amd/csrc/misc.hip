@@ -736,6 +736,21 @@ extern "C" int64_t mia_adam_workspace_bytes(int32_t ntensors) {
 // byte offset of the clip coefficient (f32) inside mia_clip_adam's workspace
 extern "C" int64_t mia_adam_coef_offset(int32_t ntensors) { return (int64_t)ntensors * ADAM_PARTS * 8; }
 
+// Pass 1 of every clip + update entry point (mia_clip_adam here, mia_clip_sgd / mia_clip_adamw in optim.hip): the
+// global gradient norm into total_norm_out and the clip coefficient into the workspace, at *coef
+int mia::clip_norm_pass(void* const* grads, const int64_t* sizes, int ntensors, int64_t max_norm_numel, float clip,
+                        float* total_norm_out, void* sqnorm_ws, const void* const* pre_sq, const int64_t* pre_n,
+                        hipStream_t s, float** coef) {
+  double* ws = reinterpret_cast<double*>(sqnorm_ws);
+  *coef = reinterpret_cast<float*>(ws + (int64_t)ntensors * ADAM_PARTS);
+  const int parts = (int)std::min<int64_t>(ADAM_PARTS, std::max<int64_t>(1, cdiv(max_norm_numel, 256 * 256)));
+  sqnorm_kernel<<<dim3(parts, ntensors), NT, 0, s>>>(grads, sizes, pre_sq, pre_n, reinterpret_cast<float*>(ws));
+  MIA_LAUNCH_CHECK("sqnorm");
+  norm_final_kernel<<<1, NF_NT, 0, s>>>(ws, ntensors, parts, clip, total_norm_out, *coef);
+  MIA_LAUNCH_CHECK("norm_final");
+  return 0;
+}
+
 extern "C" int mia_clip_adam(void* const* params, void* const* grads, void* const* exp_avg, void* const* exp_avg_sq,
                              void* const* shadow_bf16, const int64_t* sizes, int32_t ntensors, int64_t max_numel,
                              int64_t max_norm_numel, float lr, float beta1,
@@ -746,13 +761,10 @@ extern "C" int mia_clip_adam(void* const* params, void* const* grads, void* cons
   MIA_CHECK_ARG(ntensors > 0 && ntensors < 65536 && step >= 1, "clip_adam: ntensors/step");
   MIA_CHECK_ARG(!pre_sq || pre_n, "clip_adam: pre_sq needs pre_n");
   hipStream_t s = as_stream(stream);
-  double* ws = reinterpret_cast<double*>(sqnorm_ws);
-  float* coef = reinterpret_cast<float*>(ws + (int64_t)ntensors * ADAM_PARTS);
-  const int parts = (int)std::min<int64_t>(ADAM_PARTS, std::max<int64_t>(1, cdiv(max_norm_numel, 256 * 256)));
-  sqnorm_kernel<<<dim3(parts, ntensors), NT, 0, s>>>(grads, sizes, pre_sq, pre_n, reinterpret_cast<float*>(ws));
-  MIA_LAUNCH_CHECK("sqnorm");
-  norm_final_kernel<<<1, NF_NT, 0, s>>>(ws, ntensors, parts, clip, total_norm_out, coef);
-  MIA_LAUNCH_CHECK("norm_final");
+  float* coef = nullptr;
+  if (int rc = mia::clip_norm_pass(grads, sizes, ntensors, max_norm_numel, clip, total_norm_out, sqnorm_ws, pre_sq,
+                                   pre_n, s, &coef))
+    return rc;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const int ablocks = (int)std::min<int64_t>(8192, std::max<int64_t>(1, cdiv(max_numel, 256 * 32)));

@@ -176,6 +176,15 @@ SIGNATURES = {
     # include/miaudio_resample.h
     "mia_resample_out_len": (i64, [i64, i32, i32]),
     "mia_resample": (C.c_int, [vp, i64, i32, i64, vp, vp, i32, i32, i32, vp, i64, i64, vp]),
+    # include/miaudio_optim.h
+    "mia_clip_sgd": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, i64, f32, f32, f32, f32, i32, f32, vp, vp, vp, vp, vp,
+                               vp]),
+    "mia_clip_adamw": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i64, i64, f32, f32, f32, f32, f32, i32, f32, vp, vp, vp,
+                                 vp, vp, vp]),
+    "mia_gemm_sgd": (C.c_int, [P(MiaOperand), P(MiaOperand), i64, i64, i64, vp, vp, vp, i64, vp, f32, f32, f32, f32,
+                               i32, i32, vp]),
+    "mia_gemm_adamw": (C.c_int, [P(MiaOperand), P(MiaOperand), i64, i64, i64, vp, vp, vp, vp, i64, vp, f32, f32, f32,
+                                 f32, f32, f32, f32, vp]),
     "mia_last_error_string": (C.c_char_p, []),
     "mia_device_arch": (C.c_int, [C.c_char_p, i32]),
 }

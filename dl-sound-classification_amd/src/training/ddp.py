@@ -342,7 +342,7 @@ class GradAllReducer:
 
     @torch.no_grad()
     def sync_param(self, param):
-        """All-gather the f32 master rows and Adam moments of a sharded parameter, so every rank holds all of
+        """All-gather the f32 master rows and optimizer moments of a sharded parameter, so every rank holds all of
         them (a collective: every rank calls it at the same point)."""
         from ..miaudio import kernels as K
         info = getattr(param, "_mia_shard", None)
@@ -351,10 +351,9 @@ class GradAllReducer:
         _, r0, Ms, M = info
         K.wait_param(param)
         ref = getattr(param, "_mia_fused_adam", None)
-        st = getattr(ref() if callable(ref) else None, "state", {}).get(param)  # FusedAdam's moments
-        ts = [param.data]
-        if st:
-            ts += [st["exp_avg"], st["exp_avg_sq"]]
+        # the fused optimizer that owns the parameter says which moments it keeps (two, one or none)
+        moments = getattr(ref() if callable(ref) else None, "moment_tensors", None)
+        ts = [param.data] + (moments(param) if moments is not None else [])
         for t in ts:
             t2 = t.view(M, -1)
             self._all_gather(t2, t2[r0:r0 + Ms].clone())

@@ -10,8 +10,9 @@ test), accuracy on ``argmax(y)``.  Differences, all MI355X-motivated:
   * the batch's feature transform / augmentation (BC mixing for EnvNet; log-mel + SpecAugment +
     Mixup for AST) runs on the GPU inside the step (``datamodule.gpu_transform``) instead of in CPU
     DataLoader workers;
-  * ``configure_optimizers`` maps torch.optim.Adam to the fused clip+Adam kernel (FusedAdam) when the
-    parameters live on the GPU (the clip value comes from ``trainer.gradient_clip_val``).
+  * ``configure_optimizers`` maps torch.optim.Adam / AdamW / SGD to the fused clip+update kernels (FusedAdam,
+    FusedAdamW, FusedSGD) when the parameters live on the GPU (the clip value comes from
+    ``trainer.gradient_clip_val``).
 Lightning is not installed in this image; ``src.training.lite`` provides the LightningModule/Trainer
 surface this class uses (log, current_epoch, hparams, fit/test loop, DDP over RCCL).
 """
@@ -134,23 +135,37 @@ class LitClassifier(LightningModule):
         params = list(self.parameters())
         target = str(self._optim_cfg.get("_target_", "")) if self._optim_cfg is not None else ""
         optim = None
-        if params and params[0].is_cuda and target in ("torch.optim.Adam", "src.training.optim.FusedAdam"):
-            from .optim import FusedAdam
+        fused = _FUSED_OPTIMIZERS.get(target)
+        if params and params[0].is_cuda and fused is not None:
+            from . import optim as O
             kw = {k: v for k, v in self._optim_cfg.items() if k != "_target_"}
+            if target == "torch.optim.Adam" and kw.get("decoupled_weight_decay", False):
+                # torch's Adam with decoupled decay is AdamW, at Adam's default weight_decay of 0
+                fused = "FusedAdamW"
+                kw.pop("decoupled_weight_decay")
+                kw.setdefault("weight_decay", 0.0)
             clip = getattr(getattr(self, "trainer", None), "gradient_clip_val", 0.0) or 0.0
             try:
-                optim = FusedAdam(params, clip=clip, **kw)
+                optim = getattr(O, fused)(params, clip=clip, **kw)
                 optim.handles_clipping = True
-            except ValueError as e:  # an Adam option the fused kernel does not implement
-                if target != "torch.optim.Adam":
+            except ValueError as e:  # an option of torch's optimizer the fused kernel does not implement
+                if not target.startswith("torch.optim."):
                     raise
-                print(f"[engine] {e}; running torch.optim.Adam", flush=True)
+                print(f"[engine] {e}; running {target}", flush=True)
         if optim is None:
             optim = instantiate(self._optim_cfg, params=params)
         if self._sched_cfg is None:
             return optim
         sched = instantiate(self._sched_cfg, optimizer=optim)
         return {"optimizer": optim, "lr_scheduler": sched if isinstance(sched, dict) else {"scheduler": sched}}
+
+
+# optimizer targets that run as a fused clip + update step (src/training/optim.py) on GPU parameters
+_FUSED_OPTIMIZERS = {
+    "torch.optim.Adam": "FusedAdam", "src.training.optim.FusedAdam": "FusedAdam",
+    "torch.optim.AdamW": "FusedAdamW", "src.training.optim.FusedAdamW": "FusedAdamW",
+    "torch.optim.SGD": "FusedSGD", "src.training.optim.FusedSGD": "FusedSGD",
+}
 
 
 class _FusedSoftCE(torch.autograd.Function):
