@@ -30,10 +30,6 @@ namespace mia {
 void set_error(const char* fmt, ...);
 int fail(int code, const char* fmt, ...);
 int cu_count();  // compute units of the current device (cached; 256 on MI355X)
-// the global-norm pass of the clip + update entry points (misc.hip): sqnorm_kernel + norm_final_kernel
-int clip_norm_pass(void* const* grads, const int64_t* sizes, int ntensors, int64_t max_norm_numel, float clip,
-                   float* total_norm_out, void* sqnorm_ws, const void* const* pre_sq, const int64_t* pre_n,
-                   hipStream_t s, float** coef);
 }  // namespace mia
 
 #define MIA_CHECK_ARG(cond, ...)                       \

@@ -1,9 +1,11 @@
 // Dense bf16 GEMM with LDS-DMA staging, 128 x 128 tiles, gfx950 (mia_gemm path 5), with its two other modes:
 // only the per-tile sums of squares of the product (mia_gemm_sqsum_only) and the product as a weight gradient
-// consumed by a fused Adam update (mia_gemm_adam) or one of the optimizer family (mia_gemm_sgd /
-// mia_gemm_adamw); plus the sum-of-squares pass for outputs of other kernels.
+// consumed by an optimizer's update in the epilogue (mia_gemm_adam, mia_gemm_sgd, mia_gemm_adamw: one kernel body,
+// with the rule of optim_update.h the streaming kernels of optim.hip apply); plus the sum-of-squares pass for
+// outputs of other kernels.
+#include <type_traits>
+
 #include "gemm_common.h"
-#include "optim_update.h"
 #include "../../include/miaudio_optim.h"
 
 namespace {
@@ -126,10 +128,149 @@ __device__ __forceinline__ bf16x8 dfrag(const char* tile, int rbase, int ks, int
 }
 
 
+constexpr int TILE = 128 * 64 * 2;  // one operand's 128 x 64 bf16 K-tile; a kernel's one LDS array holds four
+
+// The product of RC x RC operands as a weight gradient that is never stored: the epilogue applies rule R of
+// optim_update.h (the arithmetic of the streaming kernels, with NS state tensors) to the parameter rows this tile is
+// the gradient of.  The one body of mia_gemm_adam, mia_gemm_sgd and mia_gemm_adamw: dgemm_kernel's RC x RC main
+// loop, tile order without grouping (column-block-major; row-block-major measured 2.14 -> 2.18 ms for Adam on
+// EnvNet's FC1) and full-tile staging.  dgemm_kernel keeps its own text of these: sharing them through inlined
+// functions reorders the address arithmetic of the plain instantiations, which the model GEMMs were tuned as.
+template <int NS, class R>
+__device__ __forceinline__ void dgemm_update_tile(const DArgs& g, const UpdateEpi<R>& o, char* smem) {
+  constexpr int L = MIA_LAYOUT_RC;
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int nwg = g.nbm * g.nbn;
+  const int orig = blockIdx.x;
+  const int xcd = orig % 8, q8 = nwg / 8, r8 = nwg % 8;
+  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + orig / 8;
+  const int bm = wgid % g.nbm, bn = wgid / g.nbm;
+  const int64_t m0 = (int64_t)bm * 128, n0 = (int64_t)bn * 128;
+  const int nk = (int)(g.K / 64);
+
+  DLoader<L> la;
+  DLoader<L> lb;
+  la.init(g.a, g.lda, g.M, m0, 0, wave, lane);
+  lb.init(g.b, g.ldb, g.N, n0, 0, wave, lane);
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // the parameter rows of the tile's first 16-B group per lane -- p and its state -- are fetched before the main
+  // loop, so their HBM latency hides under it; later groups are fetched one group ahead of their use
+  f32x4 pv[2][4], av[2][4], bv[2][4];
+  const int acol = (lane & 31) * 4;
+  auto fetch = [&](int it0, int b) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t off = (m0 + wave * 32 + (it0 + u) * 2 + (lane >> 5)) * o.ld + n0 + acol;
+      pv[b][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(o.p + off));
+      if constexpr (NS > 0) av[b][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(o.s0 + off));
+      if constexpr (NS > 1) bv[b][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(o.s1 + off));
+    }
+  };
+  fetch(0, 0);
+
+  if (nk > 0) {
+    la.issue(smem, wave);
+    lb.issue(smem + TILE, wave);
+  }
+  for (int kt = 0; kt < nk; ++kt) {
+    char* cur = smem + (kt & 1) * 2 * TILE;
+    if (kt + 1 < nk) {
+      char* nxt = smem + ((kt + 1) & 1) * 2 * TILE;
+      la.issue(nxt, wave);
+      lb.issue(nxt + TILE, wave);
+      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+    const char* As = cur;
+    const char* Bs = cur + TILE;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      bf16x8 fa[2], fb[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) fa[i] = dfrag<L>(As, wm * 64 + i * 32, ks, lane);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) fb[j] = dfrag<L>(Bs, wn * 64 + j * 32, ks, lane);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  }
+
+  float* tile = reinterpret_cast<float*>(smem);  // [128][128], 32-dword halves swapped on row bit 2
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int col = wn * 64 + j * 32 + (lane & 31);
+        tile[row * 128 + (col ^ (((row >> 2) & 1) << 5))] = acc[i][j][r];
+      }
+  __syncthreads();
+  // the gradient is the f32 product itself, read back as whole 512-B rows, two rows per wave instruction; every
+  // byte of p and its state is touched once, so loads and stores are non-temporal
+  const float coef = o.coef[0];
+  const bool first = o.first != 0;
+#pragma unroll
+  for (int grp = 0; grp < 4; ++grp) {
+    const int b = grp & 1;
+    if (grp + 1 < 4) fetch((grp + 1) * 4, b ^ 1);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int row = wave * 32 + (grp * 4 + u) * 2 + (lane >> 5);
+      const int64_t off = (m0 + row) * o.ld + n0 + acol;
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(tile + row * 128 + (acol ^ (((row >> 2) & 1) << 5)));
+      f32x4 p4 = pv[b][u], a4 = {0.f, 0.f, 0.f, 0.f}, b4 = a4;
+      if constexpr (NS > 0) a4 = av[b][u];
+      if constexpr (NS > 1) b4 = bv[b][u];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float sa = a4[e], sb = b4[e];
+        p4[e] = mopt::apply<NS>(o.rule, coef, first, p4[e], gv[e], sa, sb);
+        a4[e] = sa;
+        b4[e] = sb;
+      }
+      __builtin_nontemporal_store(p4, reinterpret_cast<f32x4*>(o.p + off));
+      if constexpr (NS > 0) __builtin_nontemporal_store(a4, reinterpret_cast<f32x4*>(o.s0 + off));
+      if constexpr (NS > 1) __builtin_nontemporal_store(b4, reinterpret_cast<f32x4*>(o.s1 + off));
+      if (o.shadow) {
+        const bf16x4 h4 = {(bf16)p4[0], (bf16)p4[1], (bf16)p4[2], (bf16)p4[3]};
+        __builtin_nontemporal_store(h4, reinterpret_cast<bf16x4*>(o.shadow + off));
+      }
+    }
+  }
+}
+
+// mia_gemm_sgd (NS 0 or 1) and mia_gemm_adamw
+template <int NS, class R>
+__global__ __launch_bounds__(NT) void dgemm_optim_kernel(DArgs g, UpdateEpi<R> o) {
+  __shared__ __attribute__((aligned(1024))) char smem[4 * TILE];
+  dgemm_update_tile<NS>(g, o, smem);
+}
+
 template <int LA, int LB, bool ADAM = false>
 __global__ __launch_bounds__(NT) void dgemm_kernel(DArgs g) {
-  constexpr int TILE = 128 * 64 * 2;
   __shared__ __attribute__((aligned(1024))) char smem[4 * TILE];
+  if constexpr (ADAM) {  // mia_gemm_adam, under this kernel's name: the step profile attributes the Adam step by it
+    dgemm_update_tile<2>(g, g.upd, smem);
+    return;
+  }
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wave >> 1, wn = wave & 1;
@@ -157,7 +298,7 @@ __global__ __launch_bounds__(NT) void dgemm_kernel(DArgs g) {
 
   DLoader<LA> la;
   DLoader<LB> lb;
-  la.init(g.a, g.lda, LA == MIA_LAYOUT_KC ? g.M : g.M, m0, kbeg, wave, lane);
+  la.init(g.a, g.lda, g.M, m0, kbeg, wave, lane);
   lb.init(g.b, g.ldb, g.N, n0, kbeg, wave, lane);
 
   f32x16 acc[2][2];
@@ -167,22 +308,6 @@ __global__ __launch_bounds__(NT) void dgemm_kernel(DArgs g) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // fused Adam (mode 2): the parameter rows of the tile's first 16-B group per lane -- p / m / v -- are
-  // fetched before the main loop, so their HBM latency hides under it; later groups are fetched one
-  // group ahead of their use in the epilogue
-  f32x4 pv[2][4], mv[2][4], vv[2][4];
-  const int acol = (lane & 31) * 4;
-  auto adam_fetch = [&](int it0, int b) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int64_t off = (m0 + wave * 32 + (it0 + u) * 2 + (lane >> 5)) * g.adam.ld + n0 + acol;
-      pv[b][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g.adam.p + off));
-      mv[b][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g.adam.m + off));
-      vv[b][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g.adam.v + off));
-    }
-  };
-  if constexpr (ADAM) adam_fetch(0, 0);
 
   if (nk > 0) {
     la.issue(smem, wave);
@@ -220,7 +345,7 @@ __global__ __launch_bounds__(NT) void dgemm_kernel(DArgs g) {
   // plain f32 output of a full tile (the wide weight-gradient GEMMs, e.g. EnvNet FC1: 1.38 GB of f32
   // per step): the whole 128x128 tile is staged in the (now idle) 64 KB of LDS and written as whole
   // 512-B rows, two rows per wave store instruction, non-temporal (read next by the optimizer pass)
-  const bool plain = ADAM || g.mode != 0 ||
+  const bool plain = g.mode != 0 ||
                      (g.split == 1 && g.e.dtype == MIA_F32 && g.e.act == MIA_ACT_NONE && !g.e.bias &&
                       !g.e.accumulate && !g.e.rm_inner && g.e.alpha == 1.f && m0 + 128 <= g.M && n0 + 128 <= g.N &&
                       (g.e.ldc & 3) == 0 && ((reinterpret_cast<uintptr_t>(g.e.ptr)) & 15) == 0);
@@ -252,40 +377,6 @@ __global__ __launch_bounds__(NT) void dgemm_kernel(DArgs g) {
           tile[row * 128 + (col ^ (((row >> 2) & 1) << 5))] = acc[i][j][r];
         }
     __syncthreads();
-    if constexpr (ADAM) {
-      // Adam on the parameter rows this tile is the gradient of (torch single-tensor Adam, exactly
-      // adam_kernel's arithmetic; the gradient is the f32 product itself, which is never stored)
-      const DArgs::AdamEpi& A = g.adam;
-      const float coef = A.coef[0];
-#pragma unroll
-      for (int grp = 0; grp < 4; ++grp) {
-        const int b = grp & 1;
-        if (grp + 1 < 4) adam_fetch((grp + 1) * 4, b ^ 1);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int row = wave * 32 + (grp * 4 + u) * 2 + (lane >> 5);
-          const int64_t off = (m0 + row) * A.ld + n0 + acol;
-          const f32x4 gv = *reinterpret_cast<const f32x4*>(tile + row * 128 + (acol ^ (((row >> 2) & 1) << 5)));
-          f32x4 p4 = pv[b][u], m4 = mv[b][u], v4 = vv[b][u];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float gg = fmaf(A.wd, p4[e], gv[e] * coef);
-            m4[e] = m4[e] + (1.f - A.beta1) * (gg - m4[e]);
-            v4[e] = fmaf((1.f - A.beta2) * gg, gg, v4[e] * A.beta2);
-            const float denom = sqrtf(v4[e]) / A.bc2_sqrt + A.eps;
-            p4[e] = p4[e] - A.lr_over_bc1 * (m4[e] / denom);
-          }
-          __builtin_nontemporal_store(p4, reinterpret_cast<f32x4*>(A.p + off));
-          __builtin_nontemporal_store(m4, reinterpret_cast<f32x4*>(A.m + off));
-          __builtin_nontemporal_store(v4, reinterpret_cast<f32x4*>(A.v + off));
-          if (A.shadow) {
-            const bf16x4 b4 = {(bf16)p4[0], (bf16)p4[1], (bf16)p4[2], (bf16)p4[3]};
-            __builtin_nontemporal_store(b4, reinterpret_cast<bf16x4*>(A.shadow + off));
-          }
-        }
-      }
-      return;
-    }
     float* out = reinterpret_cast<float*>(g.e.ptr);
 #pragma unroll 4
     for (int it = 0; it < 16; ++it) {
@@ -410,146 +501,10 @@ __global__ __launch_bounds__(NT) void dgemm_kernel(DArgs g) {
     tile_sqsum_store(g.e.sqsum + (int64_t)bm * g.nbn + bn, sqg, reinterpret_cast<double*>(smem));
 }
 
-// The product as a weight gradient consumed by an update of the optimizer family (mia_gemm_sgd / mia_gemm_adamw,
-// include/miaudio_optim.h).  A kernel of its own, so that dgemm_kernel<.., true> -- the Adam form, whose name and
-// code the step profile and the exactness tests pin -- stays as it is: the RC x RC main loop, tile staging and
-// one-group-ahead parameter fetch of that form, with the rule of optim_update.h in the epilogue.
-struct OptEpi {
-  float* p;
-  float* s0;           // momentum buffer (SGD) / exp_avg (AdamW)
-  float* s1;           // exp_avg_sq (AdamW)
-  bf16* shadow;        // bf16 operand copy of p, rewritten (or null)
-  const float* coef;   // device clip coefficient
-  int64_t ld;          // row stride of p / s0 / s1 / shadow (elements)
-  mopt::SgdRule sgd;
-  mopt::AdamWRule adamw;
-  int first;           // SGD: the momentum buffer is at its first use
-};
-
-template <int NS>  // state tensors beside p: 0 SGD without momentum, 1 SGD with a momentum buffer, 2 AdamW
-__global__ __launch_bounds__(NT) void dgemm_optim_kernel(DArgs g, OptEpi o) {
-  constexpr int TILE = 128 * 64 * 2;
-  constexpr int L = MIA_LAYOUT_RC;
-  __shared__ __attribute__((aligned(1024))) char smem[4 * TILE];
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int nwg = g.nbm * g.nbn;
-  const int orig = blockIdx.x;
-  const int xcd = orig % 8, q8 = nwg / 8, r8 = nwg % 8;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + orig / 8;
-  const int bm = wgid % g.nbm, bn = wgid / g.nbm;  // column-block-major, as the Adam form
-  const int64_t m0 = (int64_t)bm * 128, n0 = (int64_t)bn * 128;
-  const int nk = (int)(g.K / 64);
-
-  DLoader<L> la;
-  DLoader<L> lb;
-  la.init(g.a, g.lda, g.M, m0, 0, wave, lane);
-  lb.init(g.b, g.ldb, g.N, n0, 0, wave, lane);
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  f32x4 pv[2][4], av[2][4], bv[2][4];
-  const int acol = (lane & 31) * 4;
-  auto fetch = [&](int it0, int b) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int64_t off = (m0 + wave * 32 + (it0 + u) * 2 + (lane >> 5)) * o.ld + n0 + acol;
-      pv[b][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(o.p + off));
-      if constexpr (NS > 0) av[b][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(o.s0 + off));
-      if constexpr (NS > 1) bv[b][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(o.s1 + off));
-    }
-  };
-  fetch(0, 0);
-
-  if (nk > 0) {
-    la.issue(smem, wave);
-    lb.issue(smem + TILE, wave);
-  }
-  for (int kt = 0; kt < nk; ++kt) {
-    char* cur = smem + (kt & 1) * 2 * TILE;
-    if (kt + 1 < nk) {
-      char* nxt = smem + ((kt + 1) & 1) * 2 * TILE;
-      la.issue(nxt, wave);
-      lb.issue(nxt + TILE, wave);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    const char* As = cur;
-    const char* Bs = cur + TILE;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      bf16x8 fa[2], fb[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) fa[i] = dfrag<L>(As, wm * 64 + i * 32, ks, lane);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) fb[j] = dfrag<L>(Bs, wn * 64 + j * 32, ks, lane);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-
-  float* tile = reinterpret_cast<float*>(smem);  // [128][128], 32-dword halves swapped on row bit 2
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const int col = wn * 64 + j * 32 + (lane & 31);
-        tile[row * 128 + (col ^ (((row >> 2) & 1) << 5))] = acc[i][j][r];
-      }
-  __syncthreads();
-  const float coef = o.coef[0];
-  const bool first = o.first != 0;
-#pragma unroll
-  for (int grp = 0; grp < 4; ++grp) {
-    const int b = grp & 1;
-    if (grp + 1 < 4) fetch((grp + 1) * 4, b ^ 1);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int row = wave * 32 + (grp * 4 + u) * 2 + (lane >> 5);
-      const int64_t off = (m0 + row) * o.ld + n0 + acol;
-      const f32x4 gv = *reinterpret_cast<const f32x4*>(tile + row * 128 + (acol ^ (((row >> 2) & 1) << 5)));
-      f32x4 p4 = pv[b][u], a4 = {0.f, 0.f, 0.f, 0.f}, b4 = a4;
-      if constexpr (NS > 0) a4 = av[b][u];
-      if constexpr (NS > 1) b4 = bv[b][u];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float sa = a4[e], sb = b4[e];
-        if constexpr (NS == 2) p4[e] = mopt::adamw_update(o.adamw, coef, p4[e], gv[e], sa, sb);
-        else p4[e] = mopt::sgd_update<NS == 1>(o.sgd, coef, first, p4[e], gv[e], sa);
-        a4[e] = sa;
-        b4[e] = sb;
-      }
-      __builtin_nontemporal_store(p4, reinterpret_cast<f32x4*>(o.p + off));
-      if constexpr (NS > 0) __builtin_nontemporal_store(a4, reinterpret_cast<f32x4*>(o.s0 + off));
-      if constexpr (NS > 1) __builtin_nontemporal_store(b4, reinterpret_cast<f32x4*>(o.s1 + off));
-      if (o.shadow) {
-        const bf16x4 h4 = {(bf16)p4[0], (bf16)p4[1], (bf16)p4[2], (bf16)p4[3]};
-        __builtin_nontemporal_store(h4, reinterpret_cast<bf16x4*>(o.shadow + off));
-      }
-    }
-  }
-}
-
-template <int LA, int LB, bool ADAM = false>
+template <int LA, int LB>
 hipError_t dgemm_launch2(const DArgs& d, hipStream_t s) {
   dim3 grid((unsigned)(d.nbm * d.nbn), (unsigned)d.split);
-  dgemm_kernel<LA, LB, ADAM><<<grid, NT, 0, s>>>(d);
+  dgemm_kernel<LA, LB><<<grid, NT, 0, s>>>(d);
   return hipGetLastError();
 }
 
@@ -620,70 +575,72 @@ int tile_sqsum_run(const float* c, int64_t ldc, int64_t M, int64_t N, double* sq
 
 extern "C" int64_t mia_gemm_sqsum_slots(int64_t M, int64_t N) { return cdiv(M, 128) * cdiv(N, 128); }
 
-// The dense 128 x 128 kernel in its norm-only / fused-Adam modes (DArgs::mode): full tiles, no split.
-static int dgemm_mode(const MiaOperand* A, const MiaOperand* B, int64_t M, int64_t N, int64_t K, int mode,
-                      double* sqsum, const DArgs::AdamEpi* adam, mia_stream_t stream) {
-  MIA_CHECK_ARG(A && B, "gemm_wgrad: null descriptor");
+// The dense 128 x 128 kernel outside mia_gemm (the sums-only and the update forms): full tiles, no split.
+static int wgrad_args(const char* who, const MiaOperand* A, const MiaOperand* B, int64_t M, int64_t N, int64_t K,
+                      DArgs* d) {
+  MIA_CHECK_ARG(A && B, "%s: null descriptor", who);
   MIA_CHECK_ARG(dgemm_ok(*A, *B, M, N, K, MIA_BF16) && M % 128 == 0 && N % 128 == 0,
-                "gemm_wgrad: needs bf16 dense operands, M and N multiples of 128, K a multiple of 64");
-  DArgs d = dgemm_args(*A, *B, M, N, K, 1);
-  // sums only: row-block-major tile order (an XCD's concurrent tiles share their dY rows; 0.271 -> 0.259 ms
-  // for FC1); the Adam form keeps column-block-major (row-major measured 2.14 -> 2.18 ms)
-  d.nfast = mode == 1; d.gm = 1;
-  d.e.dtype = MIA_F32; d.e.alpha = 1.f; d.e.sqsum = sqsum;
-  d.mode = mode;
-  if (adam) d.adam = *adam;
-  hipStream_t s = as_stream(stream);
-  const int la = A->layout, lb = B->layout;
-  if (mode == 2)  // the weight-gradient layouts only (dY and X both K-major: RC x RC)
-    MIA_CHECK_ARG(la == MIA_LAYOUT_RC && lb == MIA_LAYOUT_RC, "gemm_adam: needs RC operands");
-  hipError_t err = mode == 2 ? dgemm_launch2<MIA_LAYOUT_RC, MIA_LAYOUT_RC, true>(d, s) : dgemm_launch(d, la, lb, s);
-  if (err != hipSuccess) return mia::fail(-(int)err, "gemm_wgrad launch: %s", hipGetErrorString(err));
+                "%s: needs bf16 dense operands, M and N multiples of 128, K a multiple of 64", who);
+  *d = dgemm_args(*A, *B, M, N, K, 1);
   return 0;
 }
 
 extern "C" int mia_gemm_sqsum_only(const MiaOperand* A, const MiaOperand* B, int64_t M, int64_t N, int64_t K,
                                    double* sqsum, mia_stream_t stream) {
   MIA_CHECK_ARG(sqsum, "gemm_sqsum_only: null sqsum");
-  return dgemm_mode(A, B, M, N, K, 1, sqsum, nullptr, stream);
+  DArgs d;
+  if (int rc = wgrad_args("gemm_sqsum_only", A, B, M, N, K, &d)) return rc;
+  // row-block-major tile order (an XCD's concurrent tiles share their dY rows; 0.271 -> 0.259 ms for FC1)
+  d.nfast = 1; d.gm = 1;
+  d.e.dtype = MIA_F32; d.e.alpha = 1.f; d.e.sqsum = sqsum;
+  d.mode = 1;
+  hipError_t err = dgemm_launch(d, A->layout, B->layout, as_stream(stream));
+  if (err != hipSuccess) return mia::fail(-(int)err, "gemm_sqsum_only launch: %s", hipGetErrorString(err));
+  return 0;
+}
+
+// mia_gemm_adam, mia_gemm_sgd and mia_gemm_adamw: the checks they share and the launch
+template <int NS, class R>
+static int dgemm_update(const char* who, const MiaOperand* A, const MiaOperand* B, int64_t M, int64_t N, int64_t K,
+                        const UpdateEpi<R>& o, mia_stream_t stream) {
+  DArgs d;
+  if (int rc = wgrad_args(who, A, B, M, N, K, &d)) return rc;
+  // the weight-gradient layouts only (dY and X both K-major: RC x RC)
+  MIA_CHECK_ARG(A->layout == MIA_LAYOUT_RC && B->layout == MIA_LAYOUT_RC, "%s: needs RC operands", who);
+  MIA_CHECK_ARG(o.p && o.coef && (NS < 1 || o.s0) && (NS < 2 || o.s1), "%s: null pointer", who);
+  MIA_CHECK_ARG(o.ld >= N && o.ld % 4 == 0 &&
+                    ((reinterpret_cast<uintptr_t>(o.p) | reinterpret_cast<uintptr_t>(o.s0) |
+                      reinterpret_cast<uintptr_t>(o.s1)) & 15) == 0 &&
+                    (reinterpret_cast<uintptr_t>(o.shadow) & 7) == 0,
+                "%s: parameter and state rows must be 16-B aligned (ld %% 4 == 0), the shadow 8-B aligned", who);
+  const dim3 grid((unsigned)(d.nbm * d.nbn));
+  hipStream_t s = as_stream(stream);
+  if constexpr (std::is_same_v<R, mopt::AdamRule>) {
+    d.upd = o;
+    dgemm_kernel<MIA_LAYOUT_RC, MIA_LAYOUT_RC, true><<<grid, NT, 0, s>>>(d);
+  } else {
+    dgemm_optim_kernel<NS><<<grid, NT, 0, s>>>(d, o);
+  }
+  MIA_LAUNCH_CHECK(who);
+  return 0;
 }
 
 extern "C" int mia_gemm_adam(const MiaOperand* A, const MiaOperand* B, int64_t M, int64_t N, int64_t K, float* param,
                              float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t ld, const float* coef,
                              float lr_over_bc1, float bc2_sqrt, float beta1, float beta2, float eps, float weight_decay,
                              mia_stream_t stream) {
-  MIA_CHECK_ARG(param && exp_avg && exp_avg_sq && coef, "gemm_adam: null pointer");
-  MIA_CHECK_ARG(ld >= N && ld % 4 == 0 &&
-                    ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(exp_avg) |
-                      reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(shadow_bf16) & 7) == 0,
-                "gemm_adam: p / m / v must be 16-B aligned rows (ld %% 4 == 0), the shadow 8-B aligned");
-  DArgs::AdamEpi a{param, exp_avg, exp_avg_sq, reinterpret_cast<bf16*>(shadow_bf16), coef, lr_over_bc1, bc2_sqrt,
-                   beta1, beta2, eps, weight_decay, ld};
-  return dgemm_mode(A, B, M, N, K, 2, nullptr, &a, stream);
+  const UpdateEpi<mopt::AdamRule> o{param, exp_avg, exp_avg_sq, reinterpret_cast<bf16*>(shadow_bf16), coef, ld, 0,
+                                    {lr_over_bc1, bc2_sqrt, beta1, beta2, eps, weight_decay}};
+  return dgemm_update<2>("gemm_adam", A, B, M, N, K, o, stream);
 }
 
-// ---- the optimizer family's forms of the same product (include/miaudio_optim.h): mia_gemm_adam's constraints
-static int dgemm_optim(const MiaOperand* A, const MiaOperand* B, int64_t M, int64_t N, int64_t K, const OptEpi& o,
-                       int nstate, mia_stream_t stream) {
-  MIA_CHECK_ARG(A && B, "gemm_optim: null descriptor");
-  MIA_CHECK_ARG(dgemm_ok(*A, *B, M, N, K, MIA_BF16) && M % 128 == 0 && N % 128 == 0,
-                "gemm_optim: needs bf16 dense operands, M and N multiples of 128, K a multiple of 64");
-  MIA_CHECK_ARG(A->layout == MIA_LAYOUT_RC && B->layout == MIA_LAYOUT_RC, "gemm_optim: needs RC operands");
-  MIA_CHECK_ARG(o.p && o.coef && (nstate < 1 || o.s0) && (nstate < 2 || o.s1), "gemm_optim: null pointer");
-  MIA_CHECK_ARG(o.ld >= N && o.ld % 4 == 0 &&
-                    ((reinterpret_cast<uintptr_t>(o.p) | reinterpret_cast<uintptr_t>(o.s0) |
-                      reinterpret_cast<uintptr_t>(o.s1)) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(o.shadow) & 7) == 0,
-                "gemm_optim: parameter and state rows must be 16-B aligned (ld %% 4 == 0), the shadow 8-B aligned");
-  DArgs d = dgemm_args(*A, *B, M, N, K, 1);
-  const dim3 grid((unsigned)(d.nbm * d.nbn));
-  hipStream_t s = as_stream(stream);
-  if (nstate == 0) dgemm_optim_kernel<0><<<grid, NT, 0, s>>>(d, o);
-  else if (nstate == 1) dgemm_optim_kernel<1><<<grid, NT, 0, s>>>(d, o);
-  else dgemm_optim_kernel<2><<<grid, NT, 0, s>>>(d, o);
-  MIA_LAUNCH_CHECK("gemm_optim");
-  return 0;
+extern "C" int mia_gemm_adamw(const MiaOperand* A, const MiaOperand* B, int64_t M, int64_t N, int64_t K, float* param,
+                              float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t ld, const float* coef,
+                              float lr_over_bc1, float bc2_sqrt, float beta1, float beta2, float eps, float lr,
+                              float weight_decay, mia_stream_t stream) {
+  const UpdateEpi<mopt::AdamWRule> o{param, exp_avg, exp_avg_sq, reinterpret_cast<bf16*>(shadow_bf16), coef, ld, 0,
+                                     {lr_over_bc1, bc2_sqrt, beta1, beta2, eps, mopt::adamw_decay(lr, weight_decay)}};
+  return dgemm_update<2>("gemm_adamw", A, B, M, N, K, o, stream);
 }
 
 extern "C" int mia_gemm_sgd(const MiaOperand* A, const MiaOperand* B, int64_t M, int64_t N, int64_t K, float* param,
@@ -693,20 +650,8 @@ extern "C" int mia_gemm_sgd(const MiaOperand* A, const MiaOperand* B, int64_t M,
   MIA_CHECK_ARG((momentum != 0.f) == (momentum_buf != nullptr), "gemm_sgd: momentum_buf goes with momentum != 0");
   MIA_CHECK_ARG(!nesterov || (momentum > 0.f && dampening == 0.f),
                 "gemm_sgd: nesterov needs a momentum and zero dampening");
-  OptEpi o{};
-  o.p = param; o.s0 = momentum_buf; o.shadow = reinterpret_cast<bf16*>(shadow_bf16); o.coef = coef; o.ld = ld;
-  o.sgd = mopt::SgdRule{lr, momentum, 1.f - dampening, weight_decay, nesterov ? 1 : 0};
-  o.first = first_use;
-  return dgemm_optim(A, B, M, N, K, o, momentum_buf ? 1 : 0, stream);
-}
-
-extern "C" int mia_gemm_adamw(const MiaOperand* A, const MiaOperand* B, int64_t M, int64_t N, int64_t K, float* param,
-                              float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t ld, const float* coef,
-                              float lr_over_bc1, float bc2_sqrt, float beta1, float beta2, float eps, float lr,
-                              float weight_decay, mia_stream_t stream) {
-  OptEpi o{};
-  o.p = param; o.s0 = exp_avg; o.s1 = exp_avg_sq; o.shadow = reinterpret_cast<bf16*>(shadow_bf16); o.coef = coef;
-  o.ld = ld;
-  o.adamw = mopt::AdamWRule{lr_over_bc1, bc2_sqrt, beta1, beta2, eps, mopt::adamw_decay(lr, weight_decay)};
-  return dgemm_optim(A, B, M, N, K, o, 2, stream);
+  const UpdateEpi<mopt::SgdRule> o{param, momentum_buf, nullptr, reinterpret_cast<bf16*>(shadow_bf16), coef, ld,
+                                   first_use, mopt::sgd_rule(lr, momentum, dampening, weight_decay, nesterov)};
+  return momentum_buf ? dgemm_update<1>("gemm_sgd", A, B, M, N, K, o, stream)
+                      : dgemm_update<0>("gemm_sgd", A, B, M, N, K, o, stream);
 }

@@ -3,6 +3,7 @@
 // eligibility predicate and launcher.
 #pragma once
 #include "common.h"
+#include "optim_update.h"
 
 namespace mgemm {
 
@@ -15,6 +16,20 @@ struct EpiDev {
   int64_t ldaux;
   float alpha, act_scale;
   double* sqsum;  // per-tile sum of squares of the stored output (see MiaEpilogue), or null
+};
+
+// The parameter a deferred weight gradient belongs to, updated in the epilogue of the GEMM that forms the gradient
+// (full 128 x 128 tiles, split 1) by rule R of optim_update.h
+template <class R>
+struct UpdateEpi {
+  float* p;
+  float* s0;           // momentum buffer (SGD) / exp_avg
+  float* s1;           // exp_avg_sq
+  bf16* shadow;        // bf16 operand copy of p, rewritten (or null)
+  const float* coef;   // device clip coefficient (of the clip + update entry point that ran the norm pass)
+  int64_t ld;          // row stride of p / s0 / s1 / shadow (elements)
+  int first;           // SGD: the momentum buffer is at its first use
+  R rule;
 };
 
 struct DArgs {
@@ -30,19 +45,11 @@ struct DArgs {
               // row block per XCD: ~8-11 GB per AST launch.)
   float* ws;
   EpiDev e;
-  // 0: store through e; 1: only the per-tile sums of squares of the f32 product (e.sqsum), nothing
-  // stored; 2: no store either -- the product is a weight gradient and the epilogue applies the Adam
-  // update of `adam` to the parameter it belongs to (full 128 x 128 tiles, split 1)
+  // 0: store through e; 1: only the per-tile sums of squares of the f32 product (e.sqsum), nothing stored
   int mode;
-  struct AdamEpi {
-    float* p;
-    float* m;
-    float* v;
-    bf16* shadow;        // bf16 operand copy of p, rewritten (or null)
-    const float* coef;   // device clip coefficient (mia_clip_adam's)
-    float lr_over_bc1, bc2_sqrt, beta1, beta2, eps, wd;
-    int64_t ld;          // row stride of p / m / v / shadow (elements)
-  } adam;
+  // dgemm_kernel<RC, RC, true> only (mia_gemm_adam): nothing is stored through e -- the product is a weight
+  // gradient and the epilogue applies the Adam update to the parameter it belongs to
+  UpdateEpi<mopt::AdamRule> upd;
 };
 
 // -------------------------------------------------------------------------- epilogue

@@ -1,5 +1,5 @@
-// Small kernels of the training step: weight repacking, soft-label loss, grad-norm clip + Adam,
-// dropout, AST token assembly, on-GPU BC mixing / SpecAugment+Mixup, casts (gfx950).
+// Small kernels of the training step: weight repacking, soft-label loss, dropout, AST token assembly,
+// on-GPU BC mixing / SpecAugment+Mixup, casts (gfx950).
 #include <cstdlib>
 
 #include "common.h"
@@ -212,162 +212,6 @@ __global__ __launch_bounds__(CE_NT) void soft_ce_final_kernel(int B, float* loss
     for (int w = 0; w < CE_NT / 64; ++w) { tl += wl[w]; tc += wc[w]; }
     loss_out[0] = (float)(tl / (double)B);
     if (correct_out) correct_out[0] = tc;
-  }
-}
-
-// ------------------------------------------------------------------ clip + Adam
-constexpr int ADAM_PARTS = 1024;
-constexpr int NF_NT = 1024;
-
-// Squared L2 norm partials of every gradient tensor: 16-B loads (tensor storage is 16-B aligned
-// torch allocations; a misaligned one takes the scalar path), f32 accumulation flushed to double.
-// A tensor with precomputed partials (pre_sq[tsr], e.g. the sqsum slots of the GEMM epilogue that
-// wrote it) is not re-read: its partials are summed instead, in the same fixed grid-stride order.
-__global__ __launch_bounds__(NT) void sqnorm_kernel(void* const* __restrict__ grads, const int64_t* __restrict__ sizes,
-                                                    const void* const* __restrict__ pre_sq,
-                                                    const int64_t* __restrict__ pre_n, float* __restrict__ ws) {
-  const int tsr = blockIdx.y;
-  const float* g = reinterpret_cast<const float*>(grads[tsr]);
-  const int64_t n = sizes[tsr];
-  const int64_t tid = (int64_t)blockIdx.x * NT + threadIdx.x, nthr = (int64_t)gridDim.x * NT;
-  const double* pre = pre_sq ? reinterpret_cast<const double*>(pre_sq[tsr]) : nullptr;
-  double s = 0.0;
-  float fs = 0.f;
-  int cnt = 0;
-  if (pre) {
-    for (int64_t i = tid; i < pre_n[tsr]; i += nthr) s += pre[i];
-  } else if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-    const int64_t n4 = n >> 2;
-    const float4* g4 = reinterpret_cast<const float4*>(g);
-    for (int64_t i = tid; i < n4; i += nthr) {
-      const float4 v = g4[i];
-      fs = fmaf(v.x, v.x, fs); fs = fmaf(v.y, v.y, fs); fs = fmaf(v.z, v.z, fs); fs = fmaf(v.w, v.w, fs);
-      if (++cnt == 64) { s += fs; fs = 0.f; cnt = 0; }
-    }
-    for (int64_t i = (n4 << 2) + tid; i < n; i += nthr) fs = fmaf(g[i], g[i], fs);
-  } else {
-    for (int64_t i = tid; i < n; i += nthr) {
-      fs = fmaf(g[i], g[i], fs);
-      if (++cnt == 256) { s += fs; fs = 0.f; cnt = 0; }
-    }
-  }
-  s += fs;
-  s = wave_sum_d(s);
-  __shared__ double red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    reinterpret_cast<double*>(ws)[(int64_t)tsr * ADAM_PARTS + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// ws layout (doubles): [ntensors][ADAM_PARTS] partials, then [0] = coef (float in double slot)
-__global__ __launch_bounds__(NF_NT) void norm_final_kernel(double* ws, int ntensors, int nparts, float clip,
-                                                           float* total_out, float* coef_out) {
-  double s = 0.0;
-  const int total = ntensors * nparts;
-  for (int i = threadIdx.x; i < total; i += NF_NT) {  // fixed order: deterministic
-    const int tsr = i / nparts, p = i % nparts;
-    s += ws[(int64_t)tsr * ADAM_PARTS + p];
-  }
-  s = wave_sum_d(s);
-  __shared__ double red[NF_NT / 64];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double acc = 0.0;
-    for (int w = 0; w < NF_NT / 64; ++w) acc += red[w];
-    const double tot = sqrt(acc);
-    const float totalf = (float)tot;
-    float coef = 1.f;
-    if (clip > 0.f) {
-      coef = clip / (totalf + 1e-6f);
-      if (coef > 1.f) coef = 1.f;
-    }
-    if (total_out) total_out[0] = totalf;
-    coef_out[0] = coef;
-  }
-}
-
-__global__ __launch_bounds__(NT) void adam_kernel(void* const* __restrict__ params, void* const* __restrict__ grads,
-                                                  void* const* __restrict__ m1, void* const* __restrict__ m2,
-                                                  void* const* __restrict__ shadow,
-                                                  const int64_t* __restrict__ sizes, const float* __restrict__ coef_p,
-                                                  float lr_over_bc1, float bc2_sqrt, float beta1, float beta2, float eps,
-                                                  float wd, const int32_t* __restrict__ steps, float lr) {
-  const int tsr = blockIdx.y;
-  if (!grads[tsr]) return;  // a deferred weight gradient: its update runs in its GEMM (mia_gemm_adam)
-  if (steps) {  // per-tensor step counts (a parameter that missed gradients keeps its own count, as torch's Adam)
-    const double st = (double)steps[tsr];
-    lr_over_bc1 = (float)(lr / (1.0 - pow((double)beta1, st)));
-    bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, st));
-  }
-  float* p = reinterpret_cast<float*>(params[tsr]);
-  const float* g = reinterpret_cast<const float*>(grads[tsr]);
-  float* m = reinterpret_cast<float*>(m1[tsr]);
-  float* v = reinterpret_cast<float*>(m2[tsr]);
-  bf16* sw = shadow ? reinterpret_cast<bf16*>(shadow[tsr]) : nullptr;  // bf16 operand copy of p (or none)
-  const int64_t n = sizes[tsr];
-  const float coef = coef_p[0];
-  auto upd = [&](float pv, float gv, float& mv, float& vv) {
-    gv = fmaf(wd, pv, gv * coef);
-    mv = mv + (1.f - beta1) * (gv - mv);           // exp_avg.lerp_(grad, 1 - beta1)
-    vv = fmaf((1.f - beta2) * gv, gv, vv * beta2);  // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1-beta2)
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    return pv - lr_over_bc1 * (mv / denom);
-  };
-  const int64_t tid = (int64_t)blockIdx.x * NT + threadIdx.x, nthr = (int64_t)gridDim.x * NT;
-  const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                    reinterpret_cast<uintptr_t>(v)) & 15) == 0 && (reinterpret_cast<uintptr_t>(sw) & 7) == 0;
-  int64_t done = 0;
-  if (al) {
-    // four float4 groups per iteration, all 16 loads issued before any use (one HBM round trip per
-    // 4 groups); every byte is touched once, so loads and stores are non-temporal (no L2/MALL
-    // allocation for a 10 GB once-through stream)
-    const int64_t n4 = n >> 2;
-    constexpr int U = 4;
-    f32x4* p4 = reinterpret_cast<f32x4*>(p);
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
-    f32x4* m4 = reinterpret_cast<f32x4*>(m);
-    f32x4* v4 = reinterpret_cast<f32x4*>(v);
-    auto step4 = [&](int64_t i, f32x4 pv, f32x4 gv, f32x4 mv, f32x4 vv) __attribute__((always_inline)) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float a = mv[e], b = vv[e];
-        pv[e] = upd(pv[e], gv[e], a, b);
-        mv[e] = a;
-        vv[e] = b;
-      }
-      __builtin_nontemporal_store(pv, p4 + i);
-      __builtin_nontemporal_store(mv, m4 + i);
-      __builtin_nontemporal_store(vv, v4 + i);
-      if (sw) {
-        const bf16x4 b4 = {(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
-        __builtin_nontemporal_store(b4, reinterpret_cast<bf16x4*>(sw) + i);
-      }
-    };
-    int64_t i = tid;
-    for (; i + (U - 1) * nthr < n4; i += U * nthr) {
-      f32x4 pv[U], gv[U], mv[U], vv[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t j = i + u * nthr;
-        pv[u] = __builtin_nontemporal_load(p4 + j);
-        gv[u] = __builtin_nontemporal_load(g4 + j);
-        mv[u] = __builtin_nontemporal_load(m4 + j);
-        vv[u] = __builtin_nontemporal_load(v4 + j);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) step4(i + u * nthr, pv[u], gv[u], mv[u], vv[u]);
-    }
-    for (; i < n4; i += nthr) step4(i, p4[i], g4[i], m4[i], v4[i]);
-    done = n4 << 2;
-  }
-  for (int64_t i = done + tid; i < n; i += nthr) {
-    float mv = m[i], vv = v[i];
-    p[i] = upd(p[i], g[i], mv, vv);
-    m[i] = mv;
-    v[i] = vv;
-    if (sw) sw[i] = (bf16)p[i];
   }
 }
 
@@ -726,52 +570,6 @@ extern "C" int mia_soft_ce(const float* logits, const float* y, int32_t B, int32
     soft_ce_final_kernel<<<1, CE_NT, 0, as_stream(stream)>>>(B, loss, correct);
   }
   MIA_LAUNCH_CHECK("soft_ce");
-  return 0;
-}
-
-extern "C" int64_t mia_adam_workspace_bytes(int32_t ntensors) {
-  return ((int64_t)ntensors * ADAM_PARTS + 2) * 8;
-}
-
-// byte offset of the clip coefficient (f32) inside mia_clip_adam's workspace
-extern "C" int64_t mia_adam_coef_offset(int32_t ntensors) { return (int64_t)ntensors * ADAM_PARTS * 8; }
-
-// Pass 1 of every clip + update entry point (mia_clip_adam here, mia_clip_sgd / mia_clip_adamw in optim.hip): the
-// global gradient norm into total_norm_out and the clip coefficient into the workspace, at *coef
-int mia::clip_norm_pass(void* const* grads, const int64_t* sizes, int ntensors, int64_t max_norm_numel, float clip,
-                        float* total_norm_out, void* sqnorm_ws, const void* const* pre_sq, const int64_t* pre_n,
-                        hipStream_t s, float** coef) {
-  double* ws = reinterpret_cast<double*>(sqnorm_ws);
-  *coef = reinterpret_cast<float*>(ws + (int64_t)ntensors * ADAM_PARTS);
-  const int parts = (int)std::min<int64_t>(ADAM_PARTS, std::max<int64_t>(1, cdiv(max_norm_numel, 256 * 256)));
-  sqnorm_kernel<<<dim3(parts, ntensors), NT, 0, s>>>(grads, sizes, pre_sq, pre_n, reinterpret_cast<float*>(ws));
-  MIA_LAUNCH_CHECK("sqnorm");
-  norm_final_kernel<<<1, NF_NT, 0, s>>>(ws, ntensors, parts, clip, total_norm_out, *coef);
-  MIA_LAUNCH_CHECK("norm_final");
-  return 0;
-}
-
-extern "C" int mia_clip_adam(void* const* params, void* const* grads, void* const* exp_avg, void* const* exp_avg_sq,
-                             void* const* shadow_bf16, const int64_t* sizes, int32_t ntensors, int64_t max_numel,
-                             int64_t max_norm_numel, float lr, float beta1,
-                             float beta2, float eps, float weight_decay, int32_t step, float clip,
-                             float* total_norm_out, void* sqnorm_ws, const void* const* pre_sq,
-                             const int64_t* pre_n, const int32_t* steps, mia_stream_t stream) {
-  MIA_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && sizes && sqnorm_ws, "clip_adam: null table");
-  MIA_CHECK_ARG(ntensors > 0 && ntensors < 65536 && step >= 1, "clip_adam: ntensors/step");
-  MIA_CHECK_ARG(!pre_sq || pre_n, "clip_adam: pre_sq needs pre_n");
-  hipStream_t s = as_stream(stream);
-  float* coef = nullptr;
-  if (int rc = mia::clip_norm_pass(grads, sizes, ntensors, max_norm_numel, clip, total_norm_out, sqnorm_ws, pre_sq,
-                                   pre_n, s, &coef))
-    return rc;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const int ablocks = (int)std::min<int64_t>(8192, std::max<int64_t>(1, cdiv(max_numel, 256 * 32)));
-  adam_kernel<<<dim3(ablocks, ntensors), NT, 0, s>>>(params, grads, exp_avg, exp_avg_sq, shadow_bf16, sizes, coef,
-                                                     (float)(lr / bc1), (float)sqrt(bc2), beta1, beta2, eps,
-                                                     weight_decay, steps, lr);
-  MIA_LAUNCH_CHECK("adam");
   return 0;
 }
 

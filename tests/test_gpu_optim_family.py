@@ -1,14 +1,16 @@
 """GPU: FusedSGD (mia_clip_sgd / mia_gemm_sgd) and FusedAdamW (mia_clip_adamw / mia_gemm_adamw) against the installed
 torch's clip_grad_norm_ + torch.optim.SGD / torch.optim.AdamW on the same device -- rtol 1e-5 / atol 1e-6 on the
 parameters and 1e-5 relative on the norm, what tests/test_gpu_optim.py holds FusedAdam to -- and the deferred
-weight-gradient forms against the materialised gradient, bit for bit."""
+weight-gradient forms against the materialised gradient, bit for bit.  FusedAdam (mia_clip_adam / mia_gemm_adam) runs
+the same walker and the same GEMM epilogue, so it takes the misaligned, shadow, precomputed-sum, deferred and
+position-independence cases beside them."""
 import pytest
 import torch
 
 from oracle.synth import synth_waveform
 from src.miaudio import kernels as K
 from src.miaudio import lib as L
-from src.training.optim import FusedAdamW, FusedSGD
+from src.training.optim import FusedAdam, FusedAdamW, FusedSGD
 from tests._util import envnet_with_hash_params
 
 pytestmark = pytest.mark.gpu
@@ -68,15 +70,54 @@ def test_adamw_matches_torch(cuda, clip):
     _run_against_torch(cuda, g, ps, ref, opt, torch.optim.AdamW(ref, lr=1e-2, weight_decay=1e-2), clip)
 
 
-@pytest.mark.parametrize("which", ["sgd", "sgd-plain", "adamw"])
+@pytest.mark.parametrize("which", ["sgd", "sgd-plain", "adamw", "adam"])
 def test_misaligned_views_take_the_scalar_path(cuda, which):
     g, ps, ref = _make(cuda, 2, misaligned=True)
     if which == "adamw":
         opt, ropt = FusedAdamW(ps, lr=1e-2, clip=0.5), torch.optim.AdamW(ref, lr=1e-2)
+    elif which == "adam":
+        opt = FusedAdam(ps, lr=1e-2, weight_decay=1e-2, clip=0.5)
+        ropt = torch.optim.Adam(ref, lr=1e-2, weight_decay=1e-2)
     else:
         kw = dict(momentum=0.9, nesterov=True, weight_decay=1e-4) if which == "sgd" else {}
         opt, ropt = FusedSGD(ps, lr=0.05, clip=0.5, **kw), torch.optim.SGD(ref, lr=0.05, **kw)
     _run_against_torch(cuda, g, ps, ref, opt, ropt, 0.5)
+
+
+def _family(which, ps):
+    if which == "adam":
+        return FusedAdam(ps, lr=1e-2, weight_decay=1e-2, clip=0.5), ("exp_avg", "exp_avg_sq")
+    if which == "adamw":
+        return FusedAdamW(ps, lr=1e-2, weight_decay=1e-2, clip=0.5), ("exp_avg", "exp_avg_sq")
+    if which == "sgd":
+        return FusedSGD(ps, lr=0.05, momentum=0.9, nesterov=True, weight_decay=1e-4, clip=0.5), ("momentum_buffer",)
+    return FusedSGD(ps, lr=0.05, weight_decay=1e-4, clip=0.5), ()
+
+
+@pytest.mark.parametrize("which", ["adam", "adamw", "sgd", "sgd-plain"])
+def test_update_does_not_depend_on_position_or_alignment(cuda, which):
+    """The same values once in 16-B aligned tensors and once in views at a 4-byte offset, the same (aligned)
+    gradients, 3 steps: parameters, state and norm agree bit for bit.  At 300 001 elements the grid is 37 blocks of
+    256 threads, so the aligned tensor runs the unrolled loop, the one-group remainder loop and a one-element tail;
+    1003 takes the remainder loop and a 3-element tail, 7 one group and a 3-element tail; every element of an offset
+    view goes through the element-by-element loop.  Every multiply-add of a rule is an explicit fmaf
+    (csrc/optim_update.h), so no loop can be contracted differently from another."""
+    _, pa, _ = _make(cuda, 11)
+    _, pm, _ = _make(cuda, 11, misaligned=True)
+    (oa, names), (om, _) = _family(which, pa), _family(which, pm)
+    g = torch.Generator().manual_seed(12)
+    for it in range(3):
+        for a, m in zip(pa, pm):
+            a.grad = torch.randn(a.shape, generator=g).to(cuda)
+            m.grad = a.grad.clone()
+        oa.step()
+        om.step()
+        torch.cuda.synchronize()
+        assert torch.equal(oa.last_total_norm, om.last_total_norm), it
+        for a, m in zip(pa, pm):
+            assert torch.equal(a, m), (it, a.numel())
+            for k in names:
+                assert torch.equal(oa.state[a][k], om.state[m][k]), (it, a.numel(), k)
 
 
 def test_sgd_buffer_of_a_parameter_that_missed_step_one_starts_at_step_two(cuda):
@@ -127,13 +168,15 @@ def test_sgd_table_reuse(cuda):
     assert opt.table_builds == 1
 
 
-@pytest.mark.parametrize("which", ["sgd", "sgd-plain", "adamw"])
+@pytest.mark.parametrize("which", ["sgd", "sgd-plain", "adamw", "adam"])
 def test_step_refreshes_bf16_shadow(cuda, which):
     g, ps, ref = _make(cuda, 7, sizes=(1003, 4096, 7))
     sh0 = K.bf16_shadow(ps[1])  # live copy on one tensor only
     sh2 = K.bf16_shadow(ps[0])  # and one on the tensor with a scalar tail
     if which == "adamw":
         opt = FusedAdamW(ps, lr=1e-2, clip=1.0)
+    elif which == "adam":
+        opt = FusedAdam(ps, lr=1e-2, weight_decay=1e-2, clip=1.0)
     else:
         opt = FusedSGD(ps, lr=0.05, clip=1.0, **(dict(momentum=0.9, nesterov=True) if which == "sgd" else {}))
     for it in range(3):
@@ -173,6 +216,8 @@ OPTIMIZERS = {
             ("momentum_buffer",)),
     "adamw": (lambda ps: FusedAdamW(ps, lr=1e-2, weight_decay=1e-2, clip=0.5),
               lambda ps: torch.optim.AdamW(ps, lr=1e-2, weight_decay=1e-2), ("exp_avg", "exp_avg_sq")),
+    "adam": (lambda ps: FusedAdam(ps, lr=1e-2, weight_decay=1e-2, clip=0.5),
+             lambda ps: torch.optim.Adam(ps, lr=1e-2, weight_decay=1e-2), ("exp_avg", "exp_avg_sq")),
 }
 
 
