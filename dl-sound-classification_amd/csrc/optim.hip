@@ -1,10 +1,12 @@
 // Clip + update of the fused optimizers over a device table of tensors (mia_clip_adam of include/miaudio.h,
 // mia_clip_sgd / mia_clip_adamw of include/miaudio_optim.h): one global-norm pass, then one once-through update
-// pass -- the same walker for every optimizer, with its rule of optim_update.h.
+// pass -- the same walker for every optimizer, with its rule of optim_update.h.  The two stochastic-weight-averaging
+// passes of include/miaudio_swa.h (mia_swa_update, mia_swa_transfer) are that walker with fewer streams.
 #include <algorithm>
 
 #include "optim_update.h"
 #include "../../include/miaudio_optim.h"
+#include "../../include/miaudio_swa.h"
 
 namespace {
 
@@ -257,7 +259,66 @@ int clip_adam_family(const char* who, void (*kernel)(Tables, R, const int32_t*, 
   return 0;
 }
 
+// ------------------------------------------------------------------ stochastic weight averaging
+// avg + (p - avg) / d: one subtract, one correctly rounded divide, one add -- the rounding intrinsics keep the
+// three apart (nothing to contract, no reciprocal), so the vector loops and the scalar tail give the same bits
+__device__ __forceinline__ float swa_rule(float a, float p, float d) {
+  return __fadd_rn(a, __fdiv_rn(__fsub_rn(p, a), d));
+}
+
+// avg is the walker's written tensor, the parameter its read-only one; FIRST (n_averaged == 0) copies, and the
+// unused loads of avg fall away (8 B per parameter instead of 12)
+template <bool FIRST>
+__global__ __launch_bounds__(NT) void swa_update_kernel(void* const* __restrict__ avg,
+                                                        void* const* __restrict__ params,
+                                                        const int64_t* __restrict__ sizes, float d) {
+  const int tsr = blockIdx.y;
+  stream_update<0>(reinterpret_cast<float*>(avg[tsr]), reinterpret_cast<const float*>(params[tsr]), nullptr, nullptr,
+                   nullptr, sizes[tsr],
+                   [&](float av, float pv, float&, float&) { return FIRST ? pv : swa_rule(av, pv, d); });
+}
+
+// p = avg (the old p is never loaded), the bf16 operand copy rewritten beside it as in the optimizers' pass
+__global__ __launch_bounds__(NT) void swa_transfer_kernel(void* const* __restrict__ params,
+                                                          void* const* __restrict__ avg,
+                                                          void* const* __restrict__ shadow,
+                                                          const int64_t* __restrict__ sizes) {
+  const int tsr = blockIdx.y;
+  stream_update<0>(reinterpret_cast<float*>(params[tsr]), reinterpret_cast<const float*>(avg[tsr]), nullptr, nullptr,
+                   shadow ? reinterpret_cast<bf16*>(shadow[tsr]) : nullptr, sizes[tsr],
+                   [](float, float av, float&, float&) { return av; });
+}
+
+dim3 swa_grid(int64_t max_numel, int32_t ntensors) {  // the update pass's grid (clip_pass)
+  return dim3((unsigned)std::min<int64_t>(8192, std::max<int64_t>(1, cdiv(max_numel, 256 * 32))), ntensors);
+}
+
 }  // namespace
+
+extern "C" int mia_swa_update(void* const* avg, void* const* params, const int64_t* sizes, int32_t ntensors,
+                              int64_t max_numel, int64_t n_averaged, mia_stream_t stream) {
+  MIA_CHECK_ARG(avg && params && sizes, "swa_update: null table");
+  MIA_CHECK_ARG(ntensors > 0 && ntensors < 65536, "swa_update: ntensors");
+  MIA_CHECK_ARG(n_averaged >= 0 && max_numel >= 0, "swa_update: n_averaged or max_numel < 0");
+  hipStream_t s = as_stream(stream);
+  const dim3 grid = swa_grid(max_numel, ntensors);
+  if (n_averaged == 0)
+    swa_update_kernel<true><<<grid, NT, 0, s>>>(avg, params, sizes, 1.f);
+  else
+    swa_update_kernel<false><<<grid, NT, 0, s>>>(avg, params, sizes, (float)(n_averaged + 1));
+  MIA_LAUNCH_CHECK("swa_update");
+  return 0;
+}
+
+extern "C" int mia_swa_transfer(void* const* params, void* const* avg, void* const* shadow_bf16, const int64_t* sizes,
+                                int32_t ntensors, int64_t max_numel, mia_stream_t stream) {
+  MIA_CHECK_ARG(params && avg && sizes, "swa_transfer: null table");
+  MIA_CHECK_ARG(ntensors > 0 && ntensors < 65536, "swa_transfer: ntensors");
+  MIA_CHECK_ARG(max_numel >= 0, "swa_transfer: max_numel < 0");
+  swa_transfer_kernel<<<swa_grid(max_numel, ntensors), NT, 0, as_stream(stream)>>>(params, avg, shadow_bf16, sizes);
+  MIA_LAUNCH_CHECK("swa_transfer");
+  return 0;
+}
 
 extern "C" int64_t mia_adam_workspace_bytes(int32_t ntensors) {
   return ((int64_t)ntensors * ADAM_PARTS + 2) * 8;

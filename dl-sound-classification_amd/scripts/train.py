@@ -26,6 +26,7 @@ import torch  # noqa: E402
 
 from src.training.engine import build_from_cfg  # noqa: E402
 from src.training.lite import CSVLogger, EarlyStopping, ModelCheckpoint, Trainer  # noqa: E402
+from src.training.swa import StochasticWeightAveraging  # noqa: E402
 from src.utils.config import Cfg, compose, instantiate, to_container  # noqa: E402
 
 _DM_KEYS = ("root", "fold", "val_split")
@@ -70,6 +71,12 @@ def build_callbacks(cfg):
         cbs.append(ModelCheckpoint(**to_container(cfg.checkpoint)))
     if "early_stop" in cfg:
         cbs.append(EarlyStopping(**to_container(cfg.early_stop)))
+    # no swa block in the YAML tree (as in the reference): +swa.enabled=true +swa.swa_lrs=1e-4 ...
+    swa = to_container(cfg.get("swa", {}) or {})
+    if swa.get("enabled", False):
+        extra = {k: swa[k] for k in ("annealing_epochs", "annealing_strategy") if k in swa}
+        cbs.append(StochasticWeightAveraging(swa_lrs=swa.get("swa_lrs", 1e-3),
+                                             swa_epoch_start=swa.get("swa_epoch_start", 0.75), **extra))
     return cbs
 
 

@@ -783,6 +783,75 @@ def bf16_shadow(p: torch.Tensor) -> torch.Tensor:
     return sh
 
 
+# ------------------------------------------------------------------------------------ weight averaging
+_SWA_TABLES: dict = {}  # (device, entry point) -> (key, pinned host table, device copy) of the last call
+
+
+def _swa_table(slot: str, rows, dev) -> torch.Tensor:
+    """The device pointer table of a mia_swa_* call, as _FusedOptimizer.step keeps its own: rebuilt only when a
+    pointer changed, and (with its pinned host copy) alive until the next call replaces it."""
+    key = tuple(map(tuple, rows))
+    ent = _SWA_TABLES.get((str(dev), slot))
+    if ent is None or ent[0] != key:
+        host = torch.tensor(rows, dtype=torch.int64).pin_memory()
+        ent = _SWA_TABLES[(str(dev), slot)] = (key, host, host.to(dev, non_blocking=True))
+    return ent[2]
+
+
+def _swa_check(what: str, avgs, params) -> None:
+    if not params or len(avgs) != len(params):
+        raise ValueError(f"{what}: needs one averaged tensor per parameter (got {len(avgs)} for {len(params)})")
+    for a, p in zip(avgs, params):
+        L.require_device(p, what)
+        if (a.dtype != torch.float32 or p.dtype != torch.float32 or a.shape != p.shape or a.device != p.device
+                or not a.is_contiguous() or not p.is_contiguous()):
+            raise TypeError(f"{what}: parameters and averages are contiguous f32 tensors of equal shape on one "
+                            f"device (got {tuple(p.shape)} {p.dtype} and {tuple(a.shape)} {a.dtype})")
+
+
+@torch.no_grad()
+def swa_update(avgs, params, n_averaged: int) -> None:
+    """One more sample of the running average (mia_swa_update, include/miaudio_swa.h): avg = p at
+    ``n_averaged == 0``, else avg += (p - avg) / (n_averaged + 1), over all tensors in one launch."""
+    _swa_check("swa_update", avgs, params)
+    for p in params:
+        wait_param(p)  # a row exchange of the parameter still in flight on another stream
+    dev = params[0].device
+    sizes = [p.numel() for p in params]
+    table = _swa_table("update", [[a.data_ptr() for a in avgs], [p.data_ptr() for p in params], sizes], dev)
+    with probe("swa.update", 0.0, (8 if n_averaged == 0 else 12) * sum(sizes)):
+        L.check(L.load().mia_swa_update(table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), len(params),
+                                        max(sizes), int(n_averaged), _s()), "mia_swa_update")
+
+
+@torch.no_grad()
+def swa_transfer(params, avgs) -> None:
+    """p = avg for every parameter (mia_swa_transfer); a live bf16 operand copy (bf16_shadow) is rewritten in the
+    same pass and stays valid.  Conv weight packs and MX-fp8 copies are formed from the f32 masters in every
+    forward, so the bf16 copy is the only one that could go stale."""
+    _swa_check("swa_transfer", avgs, params)
+    for p in params:
+        wait_param(p)
+    dev = params[0].device
+    shadows = [getattr(p, "_mia_bf16", None) if getattr(p, "_mia_bf16_ver", None) == p._version else None
+               for p in params]
+    shadows = [sh if sh is not None and sh.shape == p.shape and sh.device == p.device and sh.is_contiguous()
+               else None for sh, p in zip(shadows, params)]
+    sizes = [p.numel() for p in params]
+    table = _swa_table("transfer", [[p.data_ptr() for p in params], [a.data_ptr() for a in avgs],
+                                    [0 if sh is None else sh.data_ptr() for sh in shadows], sizes], dev)
+    nbytes = 8 * sum(sizes) + 2 * sum(n for n, sh in zip(sizes, shadows) if sh is not None)
+    with probe("swa.transfer", 0.0, nbytes):
+        L.check(L.load().mia_swa_transfer(table[0].data_ptr(), table[1].data_ptr(),
+                                          table[2].data_ptr() if any(sh is not None for sh in shadows) else None,
+                                          table[3].data_ptr(), len(params), max(sizes), _s()), "mia_swa_transfer")
+    for p, sh in zip(params, shadows):
+        if sh is not None:
+            p._mia_bf16_ver = p._version  # the copy matches the transferred parameter
+        else:
+            p._mia_bf16_ver = None  # the kernel wrote behind autograd's version counter: recast at the next use
+
+
 def cast(src: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     out = torch.empty(src.shape, dtype=dtype, device=src.device)
     L.check(L.load().mia_cast(src.data_ptr(), L.dtype_code(src), out.data_ptr(), L.dtype_code(out), src.numel(),

@@ -185,6 +185,9 @@ SIGNATURES = {
                                i32, i32, vp]),
     "mia_gemm_adamw": (C.c_int, [P(MiaOperand), P(MiaOperand), i64, i64, i64, vp, vp, vp, vp, i64, vp, f32, f32, f32,
                                  f32, f32, f32, f32, vp]),
+    # include/miaudio_swa.h
+    "mia_swa_update": (C.c_int, [vp, vp, vp, i32, i64, i64, vp]),
+    "mia_swa_transfer": (C.c_int, [vp, vp, vp, vp, i32, i64, vp]),
     "mia_last_error_string": (C.c_char_p, []),
     "mia_device_arch": (C.c_int, [C.c_char_p, i32]),
 }

@@ -20,6 +20,7 @@ import torch
 
 from ..miaudio import kernels as K
 from ..miaudio import lib as L
+from .bn_cma import update_factor
 
 _SEED = itertools.count(0x5EED)
 # A/B switch: conv4's backward-data without the fused ReLU+BN backward sums (a separate reduce pass)
@@ -128,7 +129,7 @@ class EnvNetFunction(torch.autograd.Function):
         def bn(i, y, P, C):
             mod = bns[i]
             return K.bn_fwd_stats(y, P, C, mod.weight, mod.bias, mod.running_mean, mod.running_var,
-                                  mod.momentum if mod.momentum is not None else 0.1, mod.eps, training)
+                                  update_factor(mod, training, False), mod.eps, training)
 
         # every conv weight's forward operand (OHWI, compute dtype) in one launch; kept for the backward's
         # (1, 2)-conv GEMMs, which take the same operand
@@ -146,7 +147,7 @@ class EnvNetFunction(torch.autograd.Function):
             if training:
                 m0 = bns[0]
                 bn1 = K.bn_finalize_shifted(st[0], st[1], B * W1, 32, p[1], m0.weight, m0.bias, m0.running_mean,
-                                            m0.running_var, m0.momentum if m0.momentum is not None else 0.1, m0.eps)
+                                            m0.running_var, update_factor(m0, training, False), m0.eps)
             else:
                 bn1 = bn(0, y1, B * W1, 32)
         else:
@@ -174,7 +175,7 @@ class EnvNetFunction(torch.autograd.Function):
             part2, nb2 = K.pool_raw_stats(y2, B, 1, W2, 64, 1, 64, p[6], p[5], win0, am0)
             m1 = bns[1]
             bn2 = K.bn_finalize_shifted(part2, nb2, B * W2, 64, p[5], m1.weight, m1.bias, m1.running_mean,
-                                        m1.running_var, m1.momentum if m1.momentum is not None else 0.1, m1.eps)
+                                        m1.running_var, update_factor(m1, training, False), m1.eps)
             K.pool_apply(win0, B, 1, Wp, 64, bn2, X0, 1)
         else:
             bn2 = bn(1, y2, B * W2, 64)
@@ -211,7 +212,7 @@ class EnvNetFunction(torch.autograd.Function):
                 mb = bns[2 + 2 * blk]
                 bna = K.bn_finalize_shifted(conv3_st[0], conv3_st[1], B * ha * wa, cout, p[pa + 1], mb.weight, mb.bias,
                                             mb.running_mean, mb.running_var,
-                                            mb.momentum if mb.momentum is not None else 0.1, mb.eps)
+                                            update_factor(mb, training, False), mb.eps)
             else:
                 bna = bn(2 + 2 * blk, ya, B * ha * wa, cout)
             _, _, cin2, cout2, kh2, kw2 = TRUNK[2 * blk + 1]
@@ -239,7 +240,7 @@ class EnvNetFunction(torch.autograd.Function):
                 mb = bns[3 + 2 * blk]
                 bnb = K.bn_finalize_shifted(conv8_st[0], conv8_st[1], B * hb * wb, cout2, p[pa + 5], mb.weight, mb.bias,
                                             mb.running_mean, mb.running_var,
-                                            mb.momentum if mb.momentum is not None else 0.1, mb.eps)
+                                            update_factor(mb, training, False), mb.eps)
             else:
                 bnb = bn(3 + 2 * blk, yb, B * hb * wb, cout2)
             ph, pw = TRUNK_POOL[blk]

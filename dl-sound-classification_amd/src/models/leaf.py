@@ -27,6 +27,7 @@ import torch.nn.functional as F_
 
 from ..miaudio import kernels as K
 from ..miaudio import lib as L
+from .bn_cma import update_factor
 
 
 class GaborFilters(nn.Module):
@@ -146,11 +147,10 @@ MLP_LAYERS = ((0, 1, 3), (4, 5, 7), (8, 9, 11))  # (Linear, BatchNorm1d, Dropout
 _SEED = itertools.count(0x1EAF)
 
 
-def _momentum(bn: nn.BatchNorm1d) -> float:
-    if bn.momentum is None:
-        raise NotImplementedError("LeafModel: BatchNorm1d(momentum=None) (cumulative moving average of the running "
-                                  "statistics) is not built; the kernels take a fixed momentum")
-    return float(bn.momentum)
+def _momentum(bn: nn.BatchNorm1d, training: bool) -> float:
+    """The update factor of this forward (momentum, or 1/k with momentum=None); a training forward is counted in
+    ``num_batches_tracked`` on the device (bn_cma.update_factor)."""
+    return update_factor(bn, training, True)
 
 
 def _trunk_params(m: "LeafModel"):
@@ -175,10 +175,8 @@ def _mlp_forward(model, p, h, cd, training):
             Wt = K.bf16_shadow(Wt)
         u = torch.empty(B, fout, dtype=tdt, device=dev)
         K.gemm(K.dense(h, L.KC, B, fin), K.dense(Wt, L.KC, fout, fin), K.epilogue(u, fout, bias=bias), B, fout, fin, cd)
-        if training:
-            bnm.num_batches_tracked.add_(1)
-        bn = K.bn_fwd_stats(u, B, fout, bnm.weight, bnm.bias, bnm.running_mean, bnm.running_var, _momentum(bnm),
-                            bnm.eps, training)
+        bn = K.bn_fwd_stats(u, B, fout, bnm.weight, bnm.bias, bnm.running_mean, bnm.running_var,
+                            _momentum(bnm, training), bnm.eps, training)
         a = K.lt_pool_apply(u.view(B, 1, fout), B, 1, fout, bn, tdt).view(B, fout)
         drop = float(model.classifier[di].p) if training else 0.0
         if drop > 0:
@@ -254,11 +252,10 @@ class _LeafTrunk(torch.autograd.Function):
 
         def finalize(bnm, z, st, rows, C, kshift):
             if training:
-                bnm.num_batches_tracked.add_(1)
                 return K.bn_finalize_shifted(st[0], st[1], rows, C, kshift, bnm.weight, bnm.bias, bnm.running_mean,
-                                             bnm.running_var, _momentum(bnm), bnm.eps)
+                                             bnm.running_var, _momentum(bnm, True), bnm.eps)
             return K.bn_fwd_stats(z, rows, C, bnm.weight, bnm.bias, bnm.running_mean, bnm.running_var,
-                                  _momentum(bnm), bnm.eps, False)
+                                  _momentum(bnm, False), bnm.eps, False)
 
         y = K.lt_pcen_fwd(P, p[0], p[1], model.pcen.eps, tdt, tag="leaf.pcen_cl.fwd")
         # forward (OHWI) packs of the three conv weights; conv1's input channels F .. Fp - 1 are zero columns

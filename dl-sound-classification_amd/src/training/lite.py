@@ -3,7 +3,8 @@
 ``Trainer(max_epochs, accelerator, precision, devices, gradient_clip_val, log_every_n_steps, ...)``
 with ``fit(module, datamodule, ckpt_path)`` / ``test(ckpt_path="best", datamodule)``, top-1
 ModelCheckpoint + EarlyStopping on a monitored metric (reference callbacks.py:32-63,
-base_training.yaml:109-123) and a CSV/JSON metrics logger in place of MLflow.
+base_training.yaml:109-123), StochasticWeightAveraging (reference callbacks.py:71-79; swa.py) and a CSV/JSON
+metrics logger in place of MLflow.
 
 Data parallelism: with ``devices > 1`` the script is launched one process per GPU
 (torch.distributed.run); the trainer joins the RCCL process group, shards the clips across ranks
@@ -23,6 +24,8 @@ from pathlib import Path
 import torch
 import torch.distributed as dist
 import torch.nn as nn
+
+from ..models.bn_cma import counts_kept
 
 
 class LightningModule(nn.Module):
@@ -178,6 +181,8 @@ class Trainer:
                           [cb for cb in cbs if isinstance(cb, ModelCheckpoint)])
         self.limits = {"train": limit_train_batches, "val": limit_val_batches, "test": limit_test_batches}
         self.should_stop = False
+        self.extra_epochs = 0      # epochs a callback adds behind max_epochs (set in its on_fit_start)
+        self.forward_only = False  # the running epoch takes no backward and no optimizer step (on_train_epoch_start)
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
         self.rank = int(os.environ.get("RANK", "0"))
         self.local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -300,25 +305,36 @@ class Trainer:
             # full resume (Lightning fit(ckpt_path=...)): weights, optimizer, LR scheduler, callback
             # state (best score / patience) and the step / epoch counters
             ck = self._load(module, ckpt_path)
-            if ck.get("optimizer_states"):
-                self.optimizer.load_state_dict(ck["optimizer_states"][0])
-            if ck.get("lr_schedulers") and self.scheduler is not None:
-                self.scheduler.load_state_dict(ck["lr_schedulers"][0])
             for cb in self.callbacks:
                 st = ck.get("callbacks", {}).get(type(cb).__name__)
                 if st is not None and hasattr(cb, "load_state_dict"):
                     cb.load_state_dict(st)
             module.global_step = int(ck.get("global_step", 0))
             start_epoch = ck.get("epoch", -1) + 1
+        # a callback may extend the loop (extra_epochs) or replace the scheduler here: on a resume its own state is
+        # loaded by now, the optimizer's and the scheduler's not yet, so a scheduler it reinstalls receives its state
+        self.extra_epochs = 0
+        self._hook("on_fit_start", module)
+        if ckpt_path:
+            if ck.get("optimizer_states"):
+                self.optimizer.load_state_dict(ck["optimizer_states"][0])
+            if ck.get("lr_schedulers") and self.scheduler is not None:
+                self.scheduler.load_state_dict(ck["lr_schedulers"][0])
         if self.world > 1:
             from .ddp import GradAllReducer
             self.ddp = GradAllReducer(module, self.world, fc1_exchange=self.fc1_exchange)
         if self.logger is not None and self.is_global_zero:
             self.logger.log_hyperparams(module.hparams)
         fused_clip = getattr(self.optimizer, "handles_clipping", False)
-        for epoch in range(start_epoch, self.max_epochs):
+        epoch = start_epoch - 1
+        while epoch + 1 < self.max_epochs + self.extra_epochs:
+            epoch += 1
             module.current_epoch = epoch
             module.train()
+            # a callback may mark the epoch about to start "forward only": one pass over the train loader in train
+            # mode without gradients, backward or optimizer step (the BatchNorm re-estimate of weight averaging)
+            self.forward_only = False
+            self._hook("on_train_epoch_start", module)
             loader = datamodule.train_dataloader()
             if hasattr(loader, "set_epoch"):
                 loader.set_epoch(epoch)
@@ -330,6 +346,15 @@ class Trainer:
                 if i >= n:
                     break
                 batch = _to(batch, self.device)
+                if self.forward_only:
+                    with torch.no_grad():
+                        module.training_step(batch, i)
+                    if self.ddp is not None and self.ddp.broadcast_buffers:
+                        # rank 0's statistics to every rank, as finish() does after a training step; every rank
+                        # counted the same forwards, so the BatchNorm counts kept on the host stay good
+                        with counts_kept(module):
+                            self.ddp._broadcast_buffers()
+                    continue
                 loss = module.training_step(batch, i)
                 loss.backward()
                 if self.ddp is not None:
@@ -369,6 +394,14 @@ class Trainer:
                 self.should_stop = bool(stop.item() > 0)
             if self.should_stop:
                 break
+        self._hook("on_train_end", module)
+
+    def _hook(self, name, module):
+        """Optional callback hooks (on_fit_start, on_train_epoch_start, on_train_end): called where defined."""
+        for cb in self.callbacks:
+            fn = getattr(cb, name, None)
+            if fn is not None:
+                fn(self, module)
 
     def test(self, module=None, ckpt_path=None, datamodule=None):
         module = module or self._module
@@ -391,3 +424,6 @@ class Trainer:
         if self.is_global_zero:
             print(json.dumps({k: round(v, 5) for k, v in logs.items()}), flush=True)
         return [logs]
+
+
+from .swa import StochasticWeightAveraging  # noqa: E402,F401  (re-exported: the callback lives in swa.py)
