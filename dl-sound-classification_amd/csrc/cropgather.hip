@@ -1,0 +1,78 @@
+// Pad-and-crop gather from a device-resident clip store (include/miaudio_data.h):
+//   out[c][b][t] = clip_{idx[b]}[start[b][c] + t - pad]  inside the clip,  +0.0f outside.
+// A plain copy: 4 B read + 4 B written per output sample, no arithmetic on the samples (moved as 32-bit words, so
+// NaN payloads and -0.0 survive).
+//
+// One thread owns one 16-B group of an output row.  Groups are cut on the row's ADDRESS, not on its index: with
+// shift = (element address of the row's first sample) & 3, group j holds t = 4 j - shift .. 4 j - shift + 3, so
+// every group that lies whole inside the row is one aligned 16-B store whatever window % 4 and the out pointer are;
+// the at most two groups that overhang the row's ends (its misaligned head and tail) store element by element.
+// The source side is misaligned against the groups in general (clip bases and crop starts are arbitrary): a lane
+// reads four consecutive words and a wave 1 KB of consecutive addresses, which the memory pipeline coalesces by
+// cache line.  Every load is guarded by 0 <= s < len of its own clip: no address is formed from an unchecked start.
+#include "common.h"
+
+#include "../../include/miaudio_data.h"
+
+namespace {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void crop_gather_kernel(const uint32_t* __restrict__ store,
+                                                          const int64_t* __restrict__ offsets, int64_t n_clips,
+                                                          const int32_t* __restrict__ idx,
+                                                          const int32_t* __restrict__ start, int32_t B, int32_t ncrop,
+                                                          int32_t pad, int32_t window, uint32_t* __restrict__ out) {
+  const int64_t rows = (int64_t)B * ncrop;
+  const int64_t out_elem = (int64_t)(reinterpret_cast<uintptr_t>(out) >> 2);
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {  // row = c * B + b
+    const int32_t c = (int32_t)(row / B), b = (int32_t)(row - (int64_t)c * B);
+    const int64_t row0 = row * window;
+    const int32_t shift = (int32_t)((out_elem + row0) & 3);
+    const int64_t t0 = 4 * j - shift;
+    if (t0 >= window) continue;
+    const int64_t i = idx[b];
+    int64_t base = 0, len = 0;
+    if (i >= 0 && i < n_clips) {
+      base = offsets[i];
+      len = offsets[i + 1] - base;
+    }
+    const int64_t s0 = (int64_t)start[(int64_t)b * ncrop + c] + t0 - pad;
+    uint32_t v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t t = t0 + k, s = s0 + k;
+      v[k] = (t >= 0 && t < window && s >= 0 && s < len) ? store[base + s] : 0u;
+    }
+    uint32_t* o = out + row0 + t0;
+    if (t0 >= 0 && t0 + 4 <= window) {
+      *reinterpret_cast<u32x4*>(o) = u32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (t0 + k >= 0 && t0 + k < window) o[k] = v[k];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int mia_crop_gather(const float* store, const int64_t* offsets, int64_t n_clips, const int32_t* idx,
+                               const int32_t* start, int32_t B, int32_t ncrop, int32_t pad, int32_t window,
+                               float* out, mia_stream_t stream) {
+  MIA_CHECK_ARG(store && offsets && idx && start && out, "crop_gather: null pointer");
+  MIA_CHECK_ARG(B >= 1 && ncrop >= 1 && window >= 1, "crop_gather: B %d, ncrop %d, window %d must be >= 1", B, ncrop,
+                window);
+  MIA_CHECK_ARG(pad >= 0 && n_clips >= 1, "crop_gather: pad %d < 0 or n_clips %lld < 1", pad, (long long)n_clips);
+  MIA_CHECK_ARG((reinterpret_cast<uintptr_t>(store) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0,
+                "crop_gather: store and out must be 4-B aligned");
+  const int64_t groups = ((int64_t)window + 3 + 3) / 4;  // a row misaligned by 3 elements
+  const int64_t rows = (int64_t)B * ncrop;
+  const dim3 grid((unsigned)cdiv(groups, 256), (unsigned)std::min<int64_t>(rows, 65535));
+  crop_gather_kernel<<<grid, 256, 0, as_stream(stream)>>>(reinterpret_cast<const uint32_t*>(store), offsets, n_clips,
+                                                          idx, start, B, ncrop, pad, window,
+                                                          reinterpret_cast<uint32_t*>(out));
+  MIA_LAUNCH_CHECK("crop_gather");
+  return 0;
+}

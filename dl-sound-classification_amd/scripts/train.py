@@ -51,7 +51,7 @@ def datamodule_config(cfg) -> dict:
           "enable_bc_mixing": ds.get("enable_bc_mixing", False),
           "enable_mixup": ds.get("enable_mixup", False),
           "mixup_alpha": ds.get("mixup_alpha", 0.5)}
-    for k in ("sample_rate", "num_clips", "clip_samples", "seed"):
+    for k in ("sample_rate", "num_clips", "clip_samples", "seed", "resident", "resident_max_gib"):
         if k in ds:
             dm[k] = ds[k]
     overrides = cfg.model.get("dataset_overrides")

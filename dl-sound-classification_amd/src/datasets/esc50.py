@@ -14,6 +14,10 @@ onto the GPU:
   resampled first, as the reference's preprocessors do (preprocessing.py:822, :1021): once, on the GPU, in
   ``setup()`` (``resample.build_store``); window, padding and the log-mel filter bank are then in target-rate
   terms.  With equal rates (the default: the target falls back to the data module's rate) nothing changes.
+* ``resident=True`` (off by default) keeps every clip in HBM (``resident.ResidentStore``, one pass
+  over the bundles) and serves the three loaders from it: the pad, the crops and the multi-crop test are one HIP
+  gather per batch (``mia_crop_gather``) and no batch touches the host.  Labels and the augmentation pool then come
+  from the store as well.
 ``SyntheticDataModule`` serves device-resident synthetic clips (benchmarks, plumbing runs).
 """
 from __future__ import annotations
@@ -112,7 +116,8 @@ class ESC50DataModule:
                  enable_bc_mixing: bool = False, enable_mixup: bool = False, mixup_alpha: float = 0.5,
                  time_mask: Union[bool, int] = False, freq_mask: Union[bool, int] = False,
                  preprocessing_mode: str = "envnet_v2", preprocessing_config: Dict | None = None,
-                 num_classes: int = 50, augment: Dict | None = None, **unused):
+                 num_classes: int = 50, augment: Dict | None = None, resident: bool = False,
+                 resident_max_gib: float = 8.0, **unused):
         if not (0 <= fold < self.NUM_FOLDS):
             raise ValueError(self._fold_error())
         self._validate_config_constraints(is_spectrogram, enable_bc_mixing, enable_mixup, time_mask, freq_mask)
@@ -135,6 +140,11 @@ class ESC50DataModule:
         self._logmel = None
         self._gen = None
         self._store = None
+        # resident=True: the clips live in HBM (resident.ResidentStore), the three loaders are
+        # _ResidentLoader objects and batches never touch the host.  Off by default: nothing changes then.
+        self.resident, self.resident_max_gib = bool(resident), float(resident_max_gib)
+        self._rstore = self._crop_gen = self._crop_table = None
+        self._loaders = {}
 
     @property
     def target_rate(self) -> int:
@@ -184,6 +194,9 @@ class ESC50DataModule:
     def setup(self, stage: str | None = None) -> None:
         if self._train_set is not None:
             return
+        if self.resident and self.device.type != "cuda":
+            raise ValueError(f"dataset.resident=true keeps the clips in HBM and crops them with a HIP kernel (there "
+                             f"is no CPU path), but the device is {self.device}: set dataset.resident=false")
         from sklearn.model_selection import StratifiedShuffleSplit
         train_folds = [f for f in range(self.NUM_FOLDS) if f != self.fold]
         if self.target_rate != self.sample_rate:
@@ -193,7 +206,17 @@ class ESC50DataModule:
             every = ESC50Dataset(self.root, folds=list(range(self.NUM_FOLDS))).files
             self._store = build_store(every, self.sample_rate, self.target_rate, self.device)
         full = self._ds(folds=train_folds, training=True)
-        labels = [full.load(i)[1] for i in range(len(full))]
+        if self.resident:
+            # one pass over the files (or none after the resampler's): waveforms and labels both come from the store
+            from . import resident as R
+            if self._store is not None:
+                self._rstore = R.from_resampled(self._store, self.device, self.resident_max_gib)
+            else:
+                every = ESC50Dataset(self.root, folds=list(range(self.NUM_FOLDS))).files
+                self._rstore = R.build_resident_store(every, self.target_rate, self.device, self.resident_max_gib)
+            labels = [self._rstore.labels_host[self._rstore.index[str(f)]] for f in full.files]
+        else:
+            labels = [full.load(i)[1] for i in range(len(full))]
         val_size = math.ceil(len(full) * self.val_split)
         splitter = StratifiedShuffleSplit(n_splits=1, test_size=val_size, random_state=42)
         tr, va = next(splitter.split(np.zeros(len(labels)), labels))
@@ -206,13 +229,21 @@ class ESC50DataModule:
         self._val_set = self._ds(files=va_files, training=False, pad_crop=True)
         self._test_set = self._ds(folds=[self.fold], training=False, pad_crop=True)
         self._train_labels = [labels[i] for i in tr]
+        ds = self._test_set
+        if self.resident and not self.is_spectrogram and ds.multi_crop_test:
+            # the multi-crop starts of every clip: torch.linspace on the host once per distinct length
+            from .resident import multi_crop_starts
+            starts, counts = multi_crop_starts(self._rstore.lengths_host, ds.pad, ds.window, ds.test_crops)
+            self._crop_table = (starts.to(self.device), counts)
 
     def _pools(self):
         """Resident augmentation pool on the device (reference preloads it for BC/Mixup, esc50.py:167-187)."""
         if self._pool is not None or not (self.enable_bc_mixing or self.enable_mixup):
             return
         ds = self._train_set
-        if self.is_spectrogram:
+        if self.resident:
+            waves = self._resident_pool_waves(ds)
+        elif self.is_spectrogram:
             waves = torch.stack([ds.load(i)[0][0] for i in range(len(ds))]).to(self.device)
         else:
             waves = torch.stack([ds.fit_window(ds.load(i)[0])[0] for i in range(len(ds))]).to(self.device)
@@ -274,19 +305,62 @@ class ESC50DataModule:
                           num_workers=self.num_workers, pin_memory=self.device.type == "cuda",
                           persistent_workers=self.num_workers > 0)
 
+    def _resident_pool_waves(self, ds):
+        """The augmentation pool's waveforms cut from the resident store with the loader's kernel: start 0, no
+        padding, one window -- ``fit_window`` (EnvNet) or the whole clip (AST; the clips must be one length, as
+        ``torch.stack`` demands on the host path)."""
+        st = self._rstore
+        sub = st.subset(ds.files)
+        window = ds.window
+        if self.is_spectrogram:
+            lens = {st.lengths_host[i] for i in sub.tolist()}
+            if len(lens) != 1:
+                raise ValueError(f"the Mixup pool holds whole clips of one length, but the training clips have "
+                                 f"{len(lens)} different lengths ({min(lens)} .. {max(lens)} samples)")
+            window = lens.pop()
+        idx = sub.to(device=self.device, dtype=torch.int32)
+        return st.gather(idx, torch.zeros_like(idx), 0, window)[0]
+
+    def _resident_loader(self, name, ds, training):
+        """One _ResidentLoader per split, kept across epochs (the trainer asks for the train loader every epoch)."""
+        if name in self._loaders:
+            return self._loaders[name]
+        from .resident import _ResidentLoader
+        st = self._rstore
+        kw = dict(batch_size=self.batch_size, window=ds.window, shuffle=training, seed=42, world=self.world,
+                  rank=self.rank)
+        if self.is_spectrogram:
+            kw.update(mode="whole", pad=0)
+        elif training:
+            if self._crop_gen is None:
+                self._crop_gen = torch.Generator(device=self.device).manual_seed(4321 + self.rank)
+            kw.update(mode="random", pad=ds.pad if ds.pad_crop else 0, gen=self._crop_gen)
+        elif ds.multi_crop_test:
+            kw.update(mode="multi", pad=ds.pad, table=self._crop_table[0], counts=self._crop_table[1])
+        else:
+            kw.update(mode="center", pad=ds.pad)
+        self._loaders[name] = _ResidentLoader(st, st.subset(ds.files), **kw)
+        return self._loaders[name]
+
     def train_dataloader(self):
         if self._train_set is None:
             raise RuntimeError("Dataset not set up. Call setup() first.")
+        if self.resident:
+            return self._resident_loader("train", self._train_set, True)
         return self._loader(self._train_set, True)
 
     def val_dataloader(self):
         if self._val_set is None:
             raise RuntimeError("Dataset not set up. Call setup() first.")
+        if self.resident:
+            return self._resident_loader("val", self._val_set, False)
         return self._loader(self._val_set, False)
 
     def test_dataloader(self):
         if self._test_set is None:
             raise RuntimeError("Dataset not set up. Call setup() first.")
+        if self.resident:
+            return self._resident_loader("test", self._test_set, False)
         return self._loader(self._test_set, False)
 
 

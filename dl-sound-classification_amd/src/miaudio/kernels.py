@@ -852,6 +852,36 @@ def swa_transfer(params, avgs) -> None:
             p._mia_bf16_ver = None  # the kernel wrote behind autograd's version counter: recast at the next use
 
 
+# ------------------------------------------------------------------------------------ resident datasets
+@torch.no_grad()
+def crop_gather(store: torch.Tensor, offsets: torch.Tensor, idx: torch.Tensor, start: torch.Tensor, pad: int,
+                window: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Pad-and-crop gather from a flat clip store (mia_crop_gather, include/miaudio_data.h): ``store`` f32 [total],
+    ``offsets`` int64 [N + 1], ``idx`` int32 [B], ``start`` int32 [B] or [B, ncrop] -> f32 [ncrop, B, window] with
+    out[c, b, t] = clip_idx[b][start[b, c] + t - pad] inside the clip and +0.0 outside.  All on one device."""
+    L.require_device(store, "crop_gather")
+    start = start.view(start.shape[0], -1)
+    B, ncrop = start.shape
+    for name, t, dt in (("store", store, torch.float32), ("offsets", offsets, torch.int64),
+                        ("idx", idx, torch.int32), ("start", start, torch.int32)):
+        if t.dtype != dt or t.device != store.device or not t.is_contiguous():
+            raise TypeError(f"crop_gather: {name} must be a contiguous {dt} tensor on {store.device} "
+                            f"(got {t.dtype} on {t.device})")
+    if idx.dim() != 1 or idx.numel() != B or offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError(f"crop_gather: idx {tuple(idx.shape)} for start {tuple(start.shape)}, "
+                         f"offsets {tuple(offsets.shape)}")
+    if out is None:
+        out = torch.empty(ncrop, B, int(window), dtype=torch.float32, device=store.device)
+    elif (out.dtype != torch.float32 or out.device != store.device or not out.is_contiguous()
+          or out.numel() != ncrop * B * int(window)):
+        raise TypeError(f"crop_gather: out must be contiguous f32 [{ncrop}, {B}, {window}] on {store.device}")
+    with probe("crop_gather", 0.0, 8.0 * out.numel()):
+        L.check(L.load().mia_crop_gather(store.data_ptr(), offsets.data_ptr(), offsets.numel() - 1, idx.data_ptr(),
+                                         start.data_ptr(), B, ncrop, int(pad), int(window), out.data_ptr(), _s()),
+                "mia_crop_gather")
+    return out
+
+
 def cast(src: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     out = torch.empty(src.shape, dtype=dtype, device=src.device)
     L.check(L.load().mia_cast(src.data_ptr(), L.dtype_code(src), out.data_ptr(), L.dtype_code(out), src.numel(),

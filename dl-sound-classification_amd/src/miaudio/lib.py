@@ -188,6 +188,8 @@ SIGNATURES = {
     # include/miaudio_swa.h
     "mia_swa_update": (C.c_int, [vp, vp, vp, i32, i64, i64, vp]),
     "mia_swa_transfer": (C.c_int, [vp, vp, vp, vp, i32, i64, vp]),
+    # include/miaudio_data.h
+    "mia_crop_gather": (C.c_int, [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp, vp]),
     "mia_last_error_string": (C.c_char_p, []),
     "mia_device_arch": (C.c_int, [C.c_char_p, i32]),
 }
