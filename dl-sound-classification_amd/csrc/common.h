@@ -46,6 +46,7 @@ int cu_count();  // compute units of the current device (cached; 256 on MI355X)
 
 static inline hipStream_t as_stream(mia_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }

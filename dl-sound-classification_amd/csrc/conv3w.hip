@@ -13,7 +13,7 @@
 // writes one f32 slab and a fixed-order reduce sums the slabs (bit-reproducible).
 #include <cstdlib>
 
-#include "common.h"
+#include "channel_partials.h"
 
 namespace {
 
@@ -220,12 +220,6 @@ __global__ __launch_bounds__(256) void conv3_wgrad_kernel(W3Args g) {
   }
 }
 
-// dbias[c] = sum over the waves' partials (f64, fixed order)
-__global__ void conv3_bias_final_kernel(const float* __restrict__ bpart, int nw, float* __restrict__ dbias) {
-  const double s = block_sum_strided(bpart + blockIdx.x, nw, 32);
-  if (threadIdx.x == 0) dbias[blockIdx.x] = (float)s;
-}
-
 // dw[e] = sum of the slabs (fixed order, bit-reproducible), e = co*64 + tap, in two coalesced stages:
 // stage 1: group g of C3_G sums its slabs in order into tmp[g][e] (double); stage 2: tmp summed in g order
 constexpr int C3_G = 64;
@@ -321,7 +315,7 @@ extern "C" int mia_conv3_wgrad_bn(const void* x, const void* da, const void* ya,
   MIA_LAUNCH_CHECK("conv3_wgrad_bn");
   conv3_wgrad_reduce1(part, nwaves, tmp, s);
   conv3_wgrad_reduce2_kernel<<<8, 256, 0, s>>>(tmp, dw);
-  conv3_bias_final_kernel<<<32, 256, 0, s>>>(a.bpart, nwaves, dbias);
+  cp_final1_kernel<<<32, 256, 0, s>>>(a.bpart, nwaves, 32, dbias);  // the waves' partials [nwaves][32] -> dbias
   MIA_LAUNCH_CHECK("conv3_wgrad_bn reduce");
   return 0;
 }

@@ -18,7 +18,7 @@
 // and used for both pixel tiles: 160 ds_read_b128 per 256 MFMAs, ~80 B/clk per CU at the MFMA peak.
 // Each wave stages its own 71-pixel strip (row pitch 80 B: conflict-free b128 reads), so the waves
 // never wait for each other; the next row's raw loads fly while the current row computes.
-#include "common.h"
+#include "channel_partials.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -328,8 +328,6 @@ __global__ __launch_bounds__(C8_NT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int mia_trunk_conv8(const void* x, const float* pre_scale, const float* pre_shift, const void* w,
@@ -339,7 +337,7 @@ extern "C" int mia_trunk_conv8(const void* x, const float* pre_scale, const floa
                 "trunk_conv8: bad arguments");
   MIA_CHECK_ARG((pre_scale == nullptr) == (pre_shift == nullptr), "trunk_conv8: pre_scale/pre_shift come together");
   MIA_CHECK_ARG(partial == nullptr || bias != nullptr, "trunk_conv8: statistics are shifted about the bias");
-  MIA_CHECK_ARG(al16(x) && al16(w) && al16(y), "trunk_conv8: x/w/y must be 16-byte aligned");
+  MIA_CHECK_ARG(aligned16(x) && aligned16(w) && aligned16(y), "trunk_conv8: x/w/y must be 16-byte aligned");
   const int oh = h + 2 * ph - 7, ow = wd + 2 * pw - 7;
   MIA_CHECK_ARG(oh > 0 && ow > 0, "trunk_conv8: output is empty");
   MIA_CHECK_ARG((int64_t)n * h * wd * 4 < (1ll << 40), "trunk_conv8: input too large");
@@ -365,19 +363,6 @@ extern "C" int mia_trunk_conv8(const void* x, const float* pre_scale, const floa
   return 0;
 }
 
-namespace {
-// per-wave partials [nw][32][2] -> dbeta[c] = sum q0, dgamma[c] = sum q1 (one block per channel, f64 sums)
-__global__ void c8_red_final_kernel(const float* __restrict__ part, int nw, float* dgamma, float* dbeta) {
-  const int c = blockIdx.x;
-  const double s1 = block_sum_strided(part + c * 2, nw, 64);
-  const double s2 = block_sum_strided(part + c * 2 + 1, nw, 64);
-  if (threadIdx.x == 0) {
-    dbeta[c] = (float)s1;
-    dgamma[c] = (float)s2;
-  }
-}
-}  // namespace
-
 extern "C" int mia_trunk_conv8_dgrad_bn(const void* dy, const void* w, void* dx, int32_t nblocks, int32_t n,
                                         int32_t h, int32_t wd, const void* bx, const float* scale,
                                         const float* shift, const float* mean, const float* invstd, float* dgamma,
@@ -385,7 +370,8 @@ extern "C" int mia_trunk_conv8_dgrad_bn(const void* dy, const void* w, void* dx,
   MIA_CHECK_ARG(dy && w && dx && bx && scale && shift && mean && invstd && dgamma && dbeta && partial && n > 0 &&
                     h > 0 && wd > 0 && nblocks > 0,
                 "trunk_conv8_dgrad_bn: bad arguments");
-  MIA_CHECK_ARG(al16(dy) && al16(w) && al16(dx) && al16(bx), "trunk_conv8_dgrad_bn: dy/w/dx/bx must be 16-byte aligned");
+  MIA_CHECK_ARG(aligned16(dy) && aligned16(w) && aligned16(dx) && aligned16(bx),
+                "trunk_conv8_dgrad_bn: dy/w/dx/bx must be 16-byte aligned");
   const int oh = h + 7, ow = wd + 7;
   MIA_CHECK_ARG((int64_t)n * oh * ow * 4 < (1ll << 40), "trunk_conv8_dgrad_bn: input too large");
   C8Args a{reinterpret_cast<const bf16*>(dy), nullptr, nullptr, reinterpret_cast<const bf16*>(w), nullptr,
@@ -398,7 +384,8 @@ extern "C" int mia_trunk_conv8_dgrad_bn(const void* dy, const void* w, void* dx,
   hipStream_t s = as_stream(stream);
   conv8_kernel<false, false, true, 2><<<nblocks, C8_NT, 0, s>>>(a);
   MIA_LAUNCH_CHECK("trunk_conv8_dgrad_bn");
-  c8_red_final_kernel<<<32, 256, 0, s>>>(partial, nw, dgamma, dbeta);
+  // per-wave partials [nw][32][2]
+  cp_final2_kernel<<<32, 256, 0, s>>>(partial, nw, 32, /*q0 = sum g*/ dbeta, /*q1 = sum g xhat*/ dgamma);
   MIA_LAUNCH_CHECK("trunk_conv8_dgrad_bn final");
   return 0;
 }

@@ -1086,7 +1086,6 @@ __global__ __launch_bounds__(64) void fw_reduce16_kernel(const float* __restrict
 // A/B switch, read at call time: MIA_REDUCE_V1=1 selects fw_reduce_kernel
 bool reduce_v1() { const char* e = getenv("MIA_REDUCE_V1"); return e && e[0] == '1'; }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // conv2 forward form: warp-specialised unless MIA_FECONV_WS=0 (A/B runs, tools/bench_fe.py FE_AB=1)
 bool fe_ws() { const char* e = getenv("MIA_FECONV_WS"); return !(e && e[0] == '0'); }

@@ -24,7 +24,7 @@
 // arithmetic of the MFMA path.
 // dw: every workgroup owns a fixed run of (clip, frame) pairs and a slab [2][F][Kt] of the workspace; the slabs
 // are added in slab order by a second kernel (no atomics: bit-identical run to run).
-#include "common.h"
+#include "pcen_math.h"
 
 namespace {
 
@@ -581,14 +581,7 @@ __global__ __launch_bounds__(256) void leaf_bwd_mfma_kernel(const float* __restr
   }
 }
 
-// ------------------------------------------------------------------------------------------- PCEN
-__device__ __forceinline__ float pcen_m(const float* __restrict__ row, int Tp, int j) {
-  float s = 0.f;
-#pragma unroll
-  for (int d = -2; d <= 2; ++d) s += (j + d >= 0 && j + d < Tp) ? row[j + d] : 0.f;
-  return s / 5.f;
-}
-
+// ------------------------------------------------------------------------------------------- PCEN (pcen_math.h)
 __global__ __launch_bounds__(256) void pcen_fwd_kernel(const float* __restrict__ P, const float* __restrict__ r,
                                                        const float* __restrict__ delta, float eps, float* __restrict__ y,
                                                        int F, int Tp, int64_t n) {
@@ -596,9 +589,7 @@ __global__ __launch_bounds__(256) void pcen_fwd_kernel(const float* __restrict__
   if (i >= n) return;
   const int64_t row = i / Tp;
   const int j = (int)(i - row * Tp), f = (int)(row % F);
-  const float* pr = P + row * Tp;
-  const float D = eps + pcen_m(pr, Tp, j);
-  y[i] = logf(pr[j] / powf(D, r[f]) + delta[f]);
+  y[i] = pcen_fwd_value(P + row * Tp, Tp, j, eps, r[f], delta[f]);
 }
 
 // grid (F, B): one (clip, filter) row; gP carries the direct path and the path through the 5-tap mean; the row's
@@ -607,7 +598,7 @@ __global__ __launch_bounds__(256) void pcen_bwd_kernel(const float* __restrict__
                                                        const float* __restrict__ delta, float eps,
                                                        const float* __restrict__ gy, float* __restrict__ gP,
                                                        double* __restrict__ part, int F, int Tp) {
-  __shared__ double red[2][256];
+  __shared__ double red[1][2][256];
   const int f = blockIdx.x, b = blockIdx.y;
   const int64_t row = (int64_t)b * F + f;
   const float* pr = P + row * Tp;
@@ -620,46 +611,21 @@ __global__ __launch_bounds__(256) void pcen_bwd_kernel(const float* __restrict__
     for (int d = -2; d <= 2; ++d) {
       const int j = i + d;
       if (j < 0 || j >= Tp) continue;
-      const float D = eps + pcen_m(pr, Tp, j);
-      const float pw = powf(D, -rf);          // D^-r
-      const float u = pr[j] * pw + df;
-      const float gu = gr[j] / u;
-      g += gu * (-rf * pr[j] * pw / D) * 0.2f;  // through M[j]
+      const PcenTap tp = pcen_bwd_tap(pr, Tp, j, eps, gr[j], rf, df);
+      g += tp.via_m;
       if (d == 0) {
-        g += gu * pw;
-        sr += (double)(gu * pr[j] * pw * -logf(D));
-        sd += (double)gu;
+        g += tp.direct;
+        sr += (double)tp.dr;
+        sd += (double)tp.ddelta;
       }
     }
     gP[row * Tp + i] = g;
   }
-  red[0][threadIdx.x] = sr;
-  red[1][threadIdx.x] = sd;
-  __syncthreads();
-  for (int wd = 128; wd > 0; wd >>= 1) {
-    if ((int)threadIdx.x < wd) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + wd];
-      red[1][threadIdx.x] += red[1][threadIdx.x + wd];
-    }
-    __syncthreads();
-  }
+  pcen_row_tree<1>(red, &sr, &sd);
   if (threadIdx.x == 0) {
-    part[row * 2] = red[0][0];
-    part[row * 2 + 1] = red[1][0];
+    part[row * 2] = red[0][0][0];
+    part[row * 2 + 1] = red[0][1][0];
   }
-}
-
-__global__ __launch_bounds__(256) void pcen_param_reduce_kernel(const double* __restrict__ part, float* __restrict__ dr,
-                                                                float* __restrict__ ddelta, int B, int F) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f >= F) return;
-  double a = 0.0, c = 0.0;
-  for (int b = 0; b < B; ++b) {
-    a += part[((int64_t)b * F + f) * 2];
-    c += part[((int64_t)b * F + f) * 2 + 1];
-  }
-  dr[f] = (float)a;
-  ddelta[f] = (float)c;
 }
 
 template <typename K>

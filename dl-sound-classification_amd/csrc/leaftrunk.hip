@@ -12,12 +12,12 @@
 // Every reduction runs in a fixed order (no atomics): results are bit-identical run to run.
 #include <algorithm>
 
-#include "common.h"
+#include "channel_partials.h"
+#include "pcen_math.h"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int LT_MAXBLK = 1024;
+constexpr int NT = CP_NT;
 
 struct Slots {
   int G, rslots;
@@ -25,34 +25,7 @@ struct Slots {
 inline Slots slots_for(int c) { return Slots{c / 8, NT / (c / 8)}; }
 
 inline int lt_blocks(int64_t units, int rslots, int per) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(units, (int64_t)rslots * per), LT_MAXBLK));
-}
-
-// block reduction of per-thread channel sums over the row slots, fixed order -> partial[block][C][2]
-__device__ __forceinline__ void lt_block_reduce(const float (&s1)[8], const float (&s2)[8], int C, int G, int rslots,
-                                                float* __restrict__ partial) {
-  __shared__ float red[NT * 16];
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { red[t * 16 + i] = s1[i]; red[t * 16 + 8 + i] = s2[i]; }
-  __syncthreads();
-  for (int e = t; e < 2 * C; e += NT) {
-    const int q = e / C, c = e - q * C, cg = c >> 3, ci = c & 7;
-    float acc = 0.f;
-    for (int r = 0; r < rslots; ++r) acc += red[(r * G + cg) * 16 + q * 8 + ci];
-    partial[((int64_t)blockIdx.x * C + c) * 2 + q] = acc;
-  }
-}
-
-// partial[nblk][C][2] -> out0[c] = sum of slot 0, out1[c] = sum of slot 1 (double, fixed order); one block per channel
-__global__ __launch_bounds__(256) void lt_final_kernel(const float* __restrict__ partial, int nblk, int C,
-                                                       float* out0, float* out1) {
-  const int c = blockIdx.x;
-  const double a = block_sum_strided(partial + (int64_t)c * 2, nblk, (int64_t)C * 2);
-  const double b = block_sum_strided(partial + (int64_t)c * 2 + 1, nblk, (int64_t)C * 2);
-  if (threadIdx.x != 0) return;
-  if (out0) out0[c] = (float)a;
-  if (out1) out1[c] = (float)b;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(units, (int64_t)rslots * per), CP_MAXBLK));
 }
 
 // ------------------------------------------------------------------------------------------- b. winners + statistics
@@ -109,7 +82,7 @@ __global__ __launch_bounds__(NT) void lt_pool_stats_kernel(const void* __restric
       }
     }
   }
-  if (partial) lt_block_reduce(s1, s2, C, G, rslots, partial);
+  if (partial) cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);
 }
 
 // ------------------------------------------------------------------------------------------- c. apply
@@ -195,7 +168,7 @@ __global__ __launch_bounds__(NT) void lt_pool_bwd_gather_kernel(const void* __re
       store8(gm, MIA_F32, off, g);
     }
   }
-  lt_block_reduce(s1, s2, C, G, rslots, partial);
+  cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);
 }
 
 // dense: dz = gamma invstd (g - dbeta / P - xhat dgamma / P), g = gm[cell] at the argmax frame, else 0; unit as in
@@ -255,18 +228,13 @@ __global__ __launch_bounds__(NT) void lt_pool_bwd_apply_kernel(const float* __re
       }
     }
   }
-  if (partial) lt_block_reduce(s1, s2, C, G, rslots, partial);
+  if (partial) cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);  // slot 1: zeros
 }
 
 // ------------------------------------------------------------------------------------------- a. channels-last PCEN
-// The arithmetic is leaf.hip's pcen_fwd_kernel / pcen_bwd_kernel expression for expression (same operation order,
-// same reduction tree), so the f32 results carry the same bits; only the side of the transpose differs.
-__device__ __forceinline__ float lt_pcen_m(const float* row, int Tp, int j) {
-  float s = 0.f;
-#pragma unroll
-  for (int d = -2; d <= 2; ++d) s += (j + d >= 0 && j + d < Tp) ? row[j + d] : 0.f;
-  return s / 5.f;
-}
+// The arithmetic is pcen_math.h's, shared with leaf.hip's pcen_fwd_kernel / pcen_bwd_kernel (same expressions, same
+// frame -> thread map, same reduction tree), so the f32 results carry the same bits; only the side of the transpose
+// differs.
 
 constexpr int PF_TF = 32, PF_TT = 64;  // forward tile: 32 filters x 64 frames
 
@@ -292,8 +260,7 @@ __global__ __launch_bounds__(NT) void lt_pcen_fwd_kernel(const float* __restrict
     float v = 0.f;
     if (f < F && j < Tp) {
       const float* pr = &pin[fl][2 - t0];  // pr[j] = P[b][f][j] for j in [t0 - 2, t0 + 66)
-      const float D = eps + lt_pcen_m(pr, Tp, j);
-      v = logf(pr[j] / powf(D, r[f]) + delta[f]);
+      v = pcen_fwd_value(pr, Tp, j, eps, r[f], delta[f]);
     }
     yo[tl][fl] = v;
   }
@@ -367,16 +334,12 @@ __global__ __launch_bounds__(NT) void lt_pcen_bwd_kernel(const float* __restrict
         for (int d = -2; d <= 2; ++d) {
           const int j = i + d;
           if (j < 0 || j >= Tp) continue;
-          const float grj = gt[j - c0 + 2][q];
-          const float D = eps + lt_pcen_m(pr, Tp, j);
-          const float pw = powf(D, -rf);          // D^-r
-          const float u = pr[j] * pw + df;
-          const float gu = grj / u;
-          g += gu * (-rf * pr[j] * pw / D) * 0.2f;  // through M[j]
+          const PcenTap tp = pcen_bwd_tap(pr, Tp, j, eps, gt[j - c0 + 2][q], rf, df);
+          g += tp.via_m;
           if (d == 0) {
-            g += gu * pw;
-            sr[q] += (double)(gu * pr[j] * pw * -logf(D));
-            sd[q] += (double)gu;
+            g += tp.direct;
+            sr[q] += (double)tp.dr;
+            sd[q] += (double)tp.ddelta;
           }
         }
         gP[((int64_t)b * F + f0 + q) * Tp + i] = g;
@@ -387,39 +350,13 @@ __global__ __launch_bounds__(NT) void lt_pcen_bwd_kernel(const float* __restrict
 #pragma unroll
   for (int q0 = 0; q0 < PB_TF; q0 += PB_RQ) {
     __syncthreads();
-#pragma unroll
-    for (int q = 0; q < PB_RQ; ++q) { red[q][0][tid] = sr[q0 + q]; red[q][1][tid] = sd[q0 + q]; }
-    __syncthreads();
-    for (int wd = 128; wd > 0; wd >>= 1) {
-      if (tid < wd) {
-#pragma unroll
-        for (int q = 0; q < PB_RQ; ++q) {
-          red[q][0][tid] += red[q][0][tid + wd];
-          red[q][1][tid] += red[q][1][tid + wd];
-        }
-      }
-      __syncthreads();
-    }
+    pcen_row_tree<PB_RQ>(red, sr + q0, sd + q0);
     if (tid < PB_RQ && f0 + q0 + tid < F) {
       const int64_t row = (int64_t)b * F + f0 + q0 + tid;
       part[row * 2] = red[tid][0][0];
       part[row * 2 + 1] = red[tid][1][0];
     }
   }
-}
-
-__global__ __launch_bounds__(256) void lt_pcen_param_reduce_kernel(const double* __restrict__ part,
-                                                                   float* __restrict__ dr, float* __restrict__ ddelta,
-                                                                   int B, int F) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f >= F) return;
-  double a = 0.0, c = 0.0;
-  for (int b = 0; b < B; ++b) {
-    a += part[((int64_t)b * F + f) * 2];
-    c += part[((int64_t)b * F + f) * 2 + 1];
-  }
-  dr[f] = (float)a;
-  ddelta[f] = (float)c;
 }
 
 int lt_check_map(const char* what, int32_t dtype, int32_t n, int32_t t, int32_t c, int32_t k) {
@@ -429,8 +366,6 @@ int lt_check_map(const char* what, int32_t dtype, int32_t n, int32_t t, int32_t 
   MIA_CHECK_ARG((int64_t)n * t * (c / 8) < (1ll << 31), "%s: too many elements for 32-bit indexing", what);
   return 0;
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int lt_pcen_check(const char* what, int32_t dtype, int32_t B, int32_t F, int32_t Tp, int32_t halo) {
   MIA_CHECK_ARG(dtype == MIA_F32 || dtype == MIA_BF16, "%s: dtype %d", what, dtype);
@@ -450,7 +385,7 @@ extern "C" int32_t mia_lt_stats_blocks(int32_t n, int32_t t, int32_t c, int32_t 
 
 extern "C" int64_t mia_lt_workspace_bytes(int32_t c) {
   if (c < 8 || c > 1024 || c % 8) return 0;
-  return (int64_t)LT_MAXBLK * c * 2 * 4;
+  return (int64_t)CP_MAXBLK * c * 2 * 4;
 }
 
 extern "C" int mia_lt_pool_stats(const void* z, int32_t dtype, int32_t n, int32_t t, int32_t c, int32_t k,
@@ -460,7 +395,7 @@ extern "C" int mia_lt_pool_stats(const void* z, int32_t dtype, int32_t n, int32_
   MIA_CHECK_ARG(z && gamma && win && argmax, "lt_pool_stats: null pointer");
   MIA_CHECK_ARG(aligned16(z) && aligned16(win) && (reinterpret_cast<uintptr_t>(argmax) & 7) == 0,
                 "lt_pool_stats: alignment");
-  MIA_CHECK_ARG(nblocks >= 1 && nblocks <= LT_MAXBLK, "lt_pool_stats: nblocks %d out of [1, %d]", nblocks, LT_MAXBLK);
+  MIA_CHECK_ARG(nblocks >= 1 && nblocks <= CP_MAXBLK, "lt_pool_stats: nblocks %d out of [1, %d]", nblocks, CP_MAXBLK);
   lt_pool_stats_kernel<<<nblocks, NT, 0, as_stream(stream)>>>(z, dtype, n, t, c, k, gamma, kshift, win, argmax, partial);
   MIA_LAUNCH_CHECK("lt_pool_stats");
   return 0;
@@ -499,7 +434,8 @@ extern "C" int mia_lt_pool_bwd_gather(const void* dout, int32_t dout_dtype, int3
   lt_pool_bwd_gather_kernel<<<nb, NT, 0, s>>>(dout, dout_dtype, mean_mode, win, dtype, n, ot, c, scale, shift, mean,
                                               invstd, gm, (float*)workspace);
   MIA_LAUNCH_CHECK("lt_pool_bwd_gather");
-  lt_final_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)workspace, nb, c, dbeta, dgamma);
+  cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)workspace, nb, c, /*q0 = sum gm*/ dbeta,
+                                               /*q1 = sum gm xhat*/ dgamma);
   MIA_LAUNCH_CHECK("lt_pool_bwd_gather_final");
   return 0;
 }
@@ -519,7 +455,7 @@ extern "C" int mia_lt_pool_bwd_apply(const float* gm, const uint8_t* argmax, con
                                              dbias ? (float*)workspace : nullptr);
   MIA_LAUNCH_CHECK("lt_pool_bwd_apply");
   if (dbias) {
-    lt_final_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)workspace, nb, c, dbias, nullptr);
+    cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)workspace, nb, c, /*q0 = sum dz*/ dbias, nullptr);
     MIA_LAUNCH_CHECK("lt_pool_bwd_apply_final");
   }
   return 0;
@@ -548,7 +484,7 @@ extern "C" int mia_lt_pcen_bwd(const float* P, const float* r, const float* delt
   lt_pcen_bwd_kernel<<<dim3((unsigned)cdiv(F, PB_TF), (unsigned)B), NT, 0, s>>>(P, r, delta, eps, gy, dtype, gP, part, F,
                                                                                Fp, Tp, halo);
   MIA_LAUNCH_CHECK("lt_pcen_bwd");
-  lt_pcen_param_reduce_kernel<<<(unsigned)cdiv(F, 256), 256, 0, s>>>(part, dr, ddelta, B, F);
+  pcen_param_reduce_kernel<<<(unsigned)cdiv(F, 256), 256, 0, s>>>(part, dr, ddelta, B, F);
   MIA_LAUNCH_CHECK("lt_pcen_bwd (reduce)");
   return 0;
 }

@@ -952,7 +952,6 @@ hipError_t launch_epi(const MArgs& a, int epi, hipStream_t s) {
   return hipGetLastError();
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

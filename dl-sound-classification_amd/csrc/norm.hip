@@ -2,35 +2,16 @@
 //
 // BN runs over channels-last (P, C) activations (P = N*H*W).  Every pass reads 16 B per lane
 // (8 channels of one pixel) and reduces per channel in two deterministic stages:
-// per-block partial sums in LDS -> f32 [nblk][C][2] slab -> one finalize kernel in double.
+// per-block partial sums in LDS -> f32 [nblk][C][2] slab -> one finalize kernel in double
+// (the protocol and its order of adds: channel_partials.h).
 // The BN *apply* never takes its own pass in the forward: the consumer GEMM applies
 // scale/shift (+ReLU) while staging its operand (MIA_PRE_AFFINE_RELU), and the pool kernel does
 // the same for the pooled layers.
-#include "common.h"
+#include "channel_partials.h"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int MAXBLK = 1024;
-
-// Reduce per-thread channel partials s1[8], s2[8] (thread owns channel group cg, row slot rs)
-// across row slots through LDS, then write the block's [C][2] partial.
-__device__ __forceinline__ void block_channel_reduce(float (&s1)[8], float (&s2)[8], int C, float* partial) {
-  __shared__ float red[NT * 16];
-  const int t = threadIdx.x;
-  const int G = C / 8;
-  const int rslots = NT / G;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { red[t * 16 + i] = s1[i]; red[t * 16 + 8 + i] = s2[i]; }
-  __syncthreads();
-  // entry e < 2C sums quantity q=(e/C) of channel c=(e%C) over the row slots
-  for (int e = t; e < 2 * C; e += NT) {
-    const int q = e / C, c = e % C, cg = c / 8, ci = c % 8;
-    float acc = 0.f;
-    for (int r = 0; r < rslots; ++r) acc += red[(r * G + cg) * 16 + q * 8 + ci];
-    partial[((int64_t)blockIdx.x * C + c) * 2 + q] = acc;
-  }
-}
+constexpr int NT = CP_NT;
 
 // ---- BN forward statistics: shifted sums about K[c] = x[0][c]
 __global__ __launch_bounds__(NT) void bn_stats_kernel(const void* __restrict__ x, int dtype, int64_t P, int C,
@@ -50,7 +31,7 @@ __global__ __launch_bounds__(NT) void bn_stats_kernel(const void* __restrict__ x
       s2[i] = fmaf(d, d, s2[i]);
     }
   }
-  block_channel_reduce(s1, s2, C, partial);
+  cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);
 }
 
 __global__ void bn_finalize_kernel(const void* __restrict__ x, int dtype, const float* __restrict__ partial,
@@ -123,18 +104,7 @@ __global__ __launch_bounds__(NT) void bn_relu_bwd_reduce_kernel(const void* __re
     }
     if (dz) store8(dz, dtype, off, g);
   }
-  block_channel_reduce(s1, s2, C, partial);
-}
-
-// partial [nblk][C][2] -> out0[c] = sum q0, out1[c] = sum q1
-__global__ void channel_partial_sum_kernel(const float* __restrict__ partial, int nblk, int C,
-                                           float* out_q1, float* out_q0) {
-  const int c = blockIdx.x;  // one block per channel
-  const double a = block_sum_strided(partial + (int64_t)c * 2, nblk, (int64_t)C * 2);
-  const double b = block_sum_strided(partial + (int64_t)c * 2 + 1, nblk, (int64_t)C * 2);
-  if (threadIdx.x != 0) return;
-  if (out_q0) out_q0[c] = (float)a;
-  if (out_q1) out_q1[c] = (float)b;
+  cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);
 }
 
 // MASK: dz is the gradient of relu(bn(x)) and the ReLU mask is recomputed from x (scale/shift),
@@ -181,7 +151,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const void* __restrict
     }
     store8(dx, dtype, off, g);
   }
-  if (partial) block_channel_reduce(s1, s2, C, partial);
+  if (partial) cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);  // slot 1: zeros
 }
 
 // ---- generic column sum over a (P, C) matrix with row stride ld (any C, scalar loads)
@@ -221,16 +191,10 @@ __global__ __launch_bounds__(NT) void colsum8_kernel(const void* __restrict__ x,
   }
 }
 
-__global__ void colsum_final_kernel(const float* __restrict__ partial, int nblk, int C, float* out) {
-  const int c = blockIdx.x;  // one block per column
-  const double s = block_sum_strided(partial + c, nblk, C);
-  if (threadIdx.x == 0) out[c] = (float)s;
-}
-
 int nblocks_for(int64_t P, int C) {
   const int rslots = NT / (C / 8);
   int64_t nb = cdiv(P, (int64_t)rslots * 8);
-  if (nb > MAXBLK) nb = MAXBLK;
+  if (nb > CP_MAXBLK) nb = CP_MAXBLK;
   if (nb < 1) nb = 1;
   return (int)nb;
 }
@@ -573,7 +537,7 @@ constexpr int LN_ROWS_PER_BLOCK = 256;
 
 extern "C" int64_t mia_bn_partial_bytes(int64_t P, int32_t C) {
   if (C < 8 || C % 8) return 0;
-  return (int64_t)MAXBLK * C * 2 * 4;
+  return (int64_t)CP_MAXBLK * C * 2 * 4;
 }
 
 extern "C" int mia_bn_fwd_stats(const void* x, int32_t dtype, int64_t P, int32_t C, const float* gamma,
@@ -626,7 +590,8 @@ extern "C" int mia_bn_relu_bwd_reduce(const void* dact, void* dz, const void* x,
   const int nb = nblocks_for(P, C);
   bn_relu_bwd_reduce_kernel<<<nb, NT, 0, s>>>(dact, dz, x, dtype, P, C, scale, shift, mean, invstd, (float*)partial);
   MIA_LAUNCH_CHECK("bn_relu_bwd_reduce");
-  channel_partial_sum_kernel<<<(unsigned)C, 256, 0, s>>>((const float*)partial, nb, C, dgamma, dbeta);
+  cp_final2_kernel<<<(unsigned)C, 256, 0, s>>>((const float*)partial, nb, C, /*q0 = sum g*/ dbeta,
+                                               /*q1 = sum g xhat*/ dgamma);
   MIA_LAUNCH_CHECK("channel_partial_sum");
   return 0;
 }
@@ -643,7 +608,7 @@ extern "C" int mia_bn_bwd_apply(const void* dz, const void* x, void* dx, int32_t
                                                dbias ? (float*)partial : nullptr);
   MIA_LAUNCH_CHECK("bn_bwd_apply");
   if (dbias) {
-    channel_partial_sum_kernel<<<(unsigned)C, 256, 0, s>>>((const float*)partial, nb, C, nullptr, dbias);
+    cp_final2_kernel<<<(unsigned)C, 256, 0, s>>>((const float*)partial, nb, C, /*q0 = sum dx*/ dbias, nullptr);
     MIA_LAUNCH_CHECK("channel_partial_sum");
   }
   return 0;
@@ -662,7 +627,7 @@ extern "C" int mia_bn_relu_bwd_apply(const void* dact, const void* x, void* dx, 
                                               dbias ? (float*)partial : nullptr, scale, shift);
   MIA_LAUNCH_CHECK("bn_relu_bwd_apply");
   if (dbias) {
-    channel_partial_sum_kernel<<<(unsigned)C, 256, 0, s>>>((const float*)partial, nb, C, nullptr, dbias);
+    cp_final2_kernel<<<(unsigned)C, 256, 0, s>>>((const float*)partial, nb, C, /*q0 = sum dx*/ dbias, nullptr);
     MIA_LAUNCH_CHECK("channel_partial_sum");
   }
   return 0;
@@ -680,7 +645,7 @@ extern "C" int mia_colsum(const void* x, int32_t dtype, int64_t P, int32_t C, in
     colsum_kernel<<<dim3(nb, (unsigned)cdiv(C, NT)), NT, 0, s>>>(x, dtype, P, C, ld, (float*)partial);
   }
   MIA_LAUNCH_CHECK("colsum");
-  colsum_final_kernel<<<(unsigned)C, 256, 0, s>>>((const float*)partial, nb, C, out);
+  cp_final1_kernel<<<(unsigned)C, 256, 0, s>>>((const float*)partial, nb, C, out);
   MIA_LAUNCH_CHECK("colsum_final");
   return 0;
 }

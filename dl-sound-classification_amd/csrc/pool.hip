@@ -7,11 +7,11 @@
 // PyTorch CPU kernel.
 #include <cstdlib>
 
-#include "common.h"
+#include "channel_partials.h"
 
 namespace {
 
-constexpr int NT = 256;
+constexpr int NT = CP_NT;
 
 // n / d for 0 <= n < 2^31 without an integer division (Granlund-Montgomery: one mul_hi, add, shift)
 struct FastDiv {
@@ -423,16 +423,7 @@ __global__ __launch_bounds__(NT) void pool_bwd_kernel(const void* __restrict__ d
     }
     store8(dz, dtype, off, g);
   }
-  __shared__ float red[NT * 16];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { red[t * 16 + i] = s1[i]; red[t * 16 + 8 + i] = s2[i]; }
-  __syncthreads();
-  for (int e = t; e < 2 * C; e += NT) {
-    const int qq = e / C, c = e % C, g2 = c / 8, ci = c % 8;
-    float acc = 0.f;
-    for (int r2 = 0; r2 < rslots; ++r2) acc += red[(r2 * G + g2) * 16 + qq * 8 + ci];
-    partial[((int64_t)blockIdx.x * C + c) * 2 + qq] = acc;
-  }
+  cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);
 }
 
 // Sparse BN reductions of the pooled backward: only the argmax position of each pooled cell carries
@@ -497,6 +488,8 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_kernel(const void* __restr
     gq[0] = make_float4(gv[0], gv[1], gv[2], gv[3]);
     gq[1] = make_float4(gv[4], gv[5], gv[6], gv[7]);
   }
+  // cp_fold<2> written out: this kernel is the MIA_POOL_V1 oracle of pool_bwd_sparse_tr_kernel
+  // (tests/test_gpu_pool_forms.py) and stays independent of the shared fold that kernel uses
   __shared__ float red[NT * 16];
 #pragma unroll
   for (int i = 0; i < 8; ++i) { red[t * 16 + i] = s1[i]; red[t * 16 + 8 + i] = s2[i]; }
@@ -613,17 +606,9 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_tr_kernel(const void* __re
       gq[0] = make_float4(gv[0], gv[1], gv[2], gv[3]);
       gq[1] = make_float4(gv[4], gv[5], gv[6], gv[7]);
     }
-    __syncthreads();
+    __syncthreads();  // also the barrier between the last tile reads and the fold's writes to red
   }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { red[t * 16 + i] = s1[i]; red[t * 16 + 8 + i] = s2[i]; }
-  __syncthreads();
-  for (int e = t; e < 2 * C; e += NT) {
-    const int qq = e / C, c = e % C, g2 = c / 8, ci = c % 8;
-    float acc = 0.f;
-    for (int r2 = 0; r2 < rslots; ++r2) acc += red[(r2 * G + g2) * 16 + qq * 8 + ci];
-    partial[((int64_t)lb * C + c) * 2 + qq] = acc;
-  }
+  cp_fold<2>(s1, s2, C, G, rslots, lb, partial, red);
 }
 
 // Dense BN backward of a pooled layer in one pass: dx = gamma*invstd*(g - dbeta/P - xhat*dgamma/P)
@@ -706,18 +691,7 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_oct_kernel(const float* 
       *reinterpret_cast<uint4*>(dx + xoff + (int64_t)j * C) = uint4{o4[0], o4[1], o4[2], o4[3]};
     }
   }
-  if (!partial) return;
-  __shared__ float red[NT * 8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) red[t * 8 + i] = s1[i];
-  __syncthreads();
-  const int rslots = NT / G;
-  for (int c = t; c < C; c += NT) {
-    const int g2 = c / 8, ci = c % 8;
-    float acc = 0.f;
-    for (int r2 = 0; r2 < rslots; ++r2) acc += red[(r2 * G + g2) * 8 + ci];
-    partial[((int64_t)blockIdx.x * C + c) * 2] = acc;
-  }
+  if (partial) cp_fold<1>(s1, nullptr, C, G, NT / G, blockIdx.x, partial);
 }
 
 // Same pass for short pool windows (kw = 2..4, the trunk's (5, 3) and (1, 2) pools): a thread owns 8
@@ -812,25 +786,14 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const float* 
       }
     }
   }
-  if (!partial) return;
-  __shared__ float red[NT * 8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) red[t * 8 + i] = s1[i];
-  __syncthreads();
-  const int rslots = NT / G;
-  for (int c = t; c < C; c += NT) {
-    const int g2 = c / 8, ci = c % 8;
-    float acc = 0.f;
-    for (int r2 = 0; r2 < rslots; ++r2) acc += red[(r2 * G + g2) * 8 + ci];
-    partial[((int64_t)blockIdx.x * C + c) * 2] = acc;
-  }
+  if (partial) cp_fold<1>(s1, nullptr, C, G, NT / G, blockIdx.x, partial);
 }
 
 #ifndef PB_UNROLL
 #define PB_UNROLL 4
 #endif
 #ifndef PB_NB
-#define PB_NB 1024
+#define PB_NB CP_MAXBLK  // the partial slab holds no more rows
 #endif
 #ifndef PB_RUNS
 #define PB_RUNS 1  // runs per thread-iteration: 1, 2, 3 measured equal within 5% (block 0: 0.34-0.36 ms)
@@ -899,26 +862,7 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_kernel(const float* __re
       store8(dx, dtype, (int64_t)r * C + cg * 8, g);
     }
   }
-  if (!partial) return;
-  __shared__ float red[NT * 8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) red[t * 8 + i] = s1[i];
-  __syncthreads();
-  for (int c = t; c < C; c += NT) {
-    const int g2 = c / 8, ci = c % 8;
-    float acc = 0.f;
-    for (int r2 = 0; r2 < rslots; ++r2) acc += red[(r2 * G + g2) * 8 + ci];
-    partial[((int64_t)blockIdx.x * C + c) * 2] = acc;
-  }
-}
-
-__global__ void partial_final_kernel(const float* __restrict__ partial, int nblk, int C, float* dgamma, float* dbeta) {
-  const int c = blockIdx.x;  // one block per channel
-  const double a = block_sum_strided(partial + (int64_t)c * 2, nblk, (int64_t)C * 2);
-  const double b = block_sum_strided(partial + (int64_t)c * 2 + 1, nblk, (int64_t)C * 2);
-  if (threadIdx.x != 0) return;
-  if (dbeta) dbeta[c] = (float)a;
-  if (dgamma) dgamma[c] = (float)b;
+  if (partial) cp_fold<1>(s1, nullptr, C, G, rslots, blockIdx.x, partial);
 }
 
 // out[b][ih][iw] = sum_ky p[b][ih-ky][iw][ky]
@@ -1023,11 +967,12 @@ extern "C" int mia_pool_bwd_bn_relu_reduce(const void* dout, int32_t out_layout,
   const int rslots = NT / (c / 8);
   const int64_t P = (int64_t)n * h * w;
   hipStream_t s = as_stream(stream);
-  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(P, (int64_t)rslots * 8), 1024));
+  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(P, (int64_t)rslots * 8), CP_MAXBLK));
   pool_bwd_kernel<<<nb, NT, 0, s>>>(dout, out_layout, argmax, x, dtype, n, h, w, c, kh, kw, scale, shift, mean,
                                     invstd, dz, (float*)partial);
   MIA_LAUNCH_CHECK("pool_bwd");
-  partial_final_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, dgamma, dbeta);
+  cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum g*/ dbeta,
+                                               /*q1 = sum g xhat*/ dgamma);
   MIA_LAUNCH_CHECK("pool_bwd_final");
   return 0;
 }
@@ -1044,7 +989,7 @@ extern "C" int mia_pool_bwd_gather(const void* dout, int32_t out_layout, const u
                 "pool_bwd_gather: bad geometry / alignment");
   const int rslots = NT / (c / 8);
   const int64_t cells = (int64_t)n * (h / kh) * (w / kw);
-  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(cells, (int64_t)rslots * 2), 1024));
+  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(cells, (int64_t)rslots * 2), CP_MAXBLK));
   hipStream_t s = as_stream(stream);
   MIA_CHECK_ARG(!win || (reinterpret_cast<uintptr_t>(win) & 15) == 0, "pool_bwd_gather: win alignment");
   // the staged form from 16 cells a block iteration on (channel runs of 32 B and more; C <= 128): the frontend's
@@ -1060,7 +1005,8 @@ extern "C" int mia_pool_bwd_gather(const void* dout, int32_t out_layout, const u
                                              mean, invstd, gm, (float*)partial);
   }
   MIA_LAUNCH_CHECK("pool_bwd_gather");
-  partial_final_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, dgamma, dbeta);
+  cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum g*/ dbeta,
+                                               /*q1 = sum g xhat*/ dgamma);
   MIA_LAUNCH_CHECK("pool_bwd_gather_final");
   return 0;
 }
@@ -1081,14 +1027,14 @@ extern "C" int mia_pool_bn_relu_bwd_apply(const float* gm, const uint8_t* argmax
   const int64_t units = (int64_t)n * h * ((w + 7) / 8) * (c / 8);
   if (kw % 8 == 0 && dtype == MIA_BF16 && units < (1ll << 31) &&
       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(units, NT), 1024));  // partial slab: <= 1024 blocks
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(units, NT), CP_MAXBLK));
     pool_bn_bwd_apply_oct_kernel<<<nb, NT, 0, s>>>(gm, argmax, reinterpret_cast<const bf16*>(x), n, h, w, c, kh, kw,
                                                    make_fastdiv((w + 7) / 8), make_fastdiv(h), make_fastdiv(c / 8),
                                                    gamma, mean, invstd, dgamma, dbeta, reinterpret_cast<bf16*>(dx),
                                                    dbias ? (float*)partial : nullptr);
     MIA_LAUNCH_CHECK("pool_bn_bwd_apply");
     if (dbias) {
-      partial_final_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, nullptr, dbias);
+      cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
       MIA_LAUNCH_CHECK("pool_bn_bwd_apply_final");
     }
     return 0;
@@ -1114,18 +1060,18 @@ extern "C" int mia_pool_bn_relu_bwd_apply(const float* gm, const uint8_t* argmax
                                                             invstd, dgamma, dbeta, dxb, part);
     MIA_LAUNCH_CHECK("pool_bn_bwd_apply_run");
     if (dbias) {
-      partial_final_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, nullptr, dbias);
+      cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
       MIA_LAUNCH_CHECK("pool_bn_bwd_apply_final");
     }
     return 0;
   }
-  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(P, (int64_t)rslots * 8), 1024));
+  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(P, (int64_t)rslots * 8), CP_MAXBLK));
   pool_bn_bwd_apply_kernel<<<nb, NT, 0, s>>>(gm, argmax, x, dtype, n, h, w, c, kh, kw, make_fastdiv(w), make_fastdiv(h),
                                              make_fastdiv(kw), make_fastdiv(kh), gamma, mean, invstd, dgamma,
                                              dbeta, dx, dbias ? (float*)partial : nullptr);
   MIA_LAUNCH_CHECK("pool_bn_bwd_apply");
   if (dbias) {
-    partial_final_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, nullptr, dbias);
+    cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
     MIA_LAUNCH_CHECK("pool_bn_bwd_apply_final");
   }
   return 0;

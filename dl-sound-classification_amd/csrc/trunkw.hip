@@ -112,14 +112,13 @@ int grid_for(int64_t work) {
   return (int)(b < 8192 ? (b > 0 ? b : 1) : 8192);
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
 extern "C" int mia_bn_relu_apply(const void* x, int64_t P, int32_t C, const float* scale, const float* shift,
                                  void* out, mia_stream_t stream) {
   MIA_CHECK_ARG(x && scale && shift && out && P > 0 && C > 0 && C % 8 == 0, "bn_relu_apply: bad arguments");
-  MIA_CHECK_ARG(al16(x) && al16(out), "bn_relu_apply: x / out must be 16-byte aligned");
+  MIA_CHECK_ARG(aligned16(x) && aligned16(out), "bn_relu_apply: x / out must be 16-byte aligned");
   bn_relu_apply_kernel<<<grid_for(P * (C / 8)), 256, 0, as_stream(stream)>>>(
       reinterpret_cast<const bf16*>(x), P, C, scale, shift, reinterpret_cast<bf16*>(out));
   MIA_LAUNCH_CHECK("bn_relu_apply");
@@ -128,7 +127,7 @@ extern "C" int mia_bn_relu_apply(const void* x, int64_t P, int32_t C, const floa
 
 extern "C" int mia_shift_pad_w2(const void* dy, int64_t rows, int32_t w, int32_t c, void* out, mia_stream_t stream) {
   MIA_CHECK_ARG(dy && out && rows > 0 && w >= 2 && c > 0 && c % 8 == 0, "shift_pad_w2: bad arguments");
-  MIA_CHECK_ARG(al16(dy) && al16(out), "shift_pad_w2: dy / out must be 16-byte aligned");
+  MIA_CHECK_ARG(aligned16(dy) && aligned16(out), "shift_pad_w2: dy / out must be 16-byte aligned");
   shift_pad2_kernel<<<grid_for(rows * w * (c / 8)), 256, 0, as_stream(stream)>>>(
       reinterpret_cast<const bf16*>(dy), rows, w, c, reinterpret_cast<bf16*>(out));
   MIA_LAUNCH_CHECK("shift_pad_w2");
@@ -139,7 +138,7 @@ extern "C" int mia_pad_w2(const void* dy, int64_t rows, int32_t w, int32_t c, vo
                           int32_t zc, mia_stream_t stream) {
   MIA_CHECK_ARG(dy && dst && rows > 0 && w >= 2 && c > 0 && c % 8 == 0 && zc % 8 == 0 && (zc == 0 || zero_pixel),
                 "pad_w2: bad arguments");
-  MIA_CHECK_ARG(al16(dy) && al16(dst) && (!zero_pixel || al16(zero_pixel)), "pad_w2: 16-byte aligned pointers");
+  MIA_CHECK_ARG(aligned16(dy) && aligned16(dst) && (!zero_pixel || aligned16(zero_pixel)), "pad_w2: 16-byte aligned pointers");
   pad_w2_kernel<<<grid_for((1 + rows * w) * (c / 8)), 256, 0, as_stream(stream)>>>(
       reinterpret_cast<const u32x4*>(dy), rows, w, c / 8, reinterpret_cast<u32x4*>(dst),
       reinterpret_cast<u32x4*>(zero_pixel), zc / 8);
@@ -149,7 +148,7 @@ extern "C" int mia_pad_w2(const void* dy, int64_t rows, int32_t w, int32_t c, vo
 
 extern "C" int mia_drop_last_col(const void* src, int64_t rows, int32_t w, int32_t c, void* dst, mia_stream_t stream) {
   MIA_CHECK_ARG(src && dst && rows > 0 && w >= 2 && c > 0 && c % 8 == 0, "drop_last_col: bad arguments");
-  MIA_CHECK_ARG(al16(src) && al16(dst), "drop_last_col: src / dst must be 16-byte aligned");
+  MIA_CHECK_ARG(aligned16(src) && aligned16(dst), "drop_last_col: src / dst must be 16-byte aligned");
   drop_last_col_kernel<<<grid_for(rows * (w - 1) * (c / 8)), 256, 0, as_stream(stream)>>>(
       reinterpret_cast<const u32x4*>(src), rows, w, c / 8, reinterpret_cast<u32x4*>(dst));
   MIA_LAUNCH_CHECK("drop_last_col");
