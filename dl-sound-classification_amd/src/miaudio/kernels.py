@@ -882,6 +882,94 @@ def crop_gather(store: torch.Tensor, offsets: torch.Tensor, idx: torch.Tensor, s
     return out
 
 
+# ------------------------------------------------------------------------------------ WAV ingestion
+def _check_flat(name: str, what: str, t: torch.Tensor, dt, device):
+    if t.dtype != dt or t.device != device or not t.is_contiguous() or t.dim() != 1:
+        raise TypeError(f"{what}: {name} must be a contiguous 1-D {dt} tensor on {device} "
+                        f"(got {t.dtype} {tuple(t.shape)} on {t.device})")
+
+
+def pcm_decode(data: torch.Tensor, clips, out_offsets, out: torch.Tensor):
+    """Decode, downmix and take the peak of the clips staged in ``data`` (mia_pcm_decode, include/miaudio_wav.h).
+
+    ``data``: uint8 device tensor of sample bytes; ``clips``: one ``(byte_off, frames, channels, format)`` per clip
+    (host ints, format one of ``L.PCM_*``); ``out_offsets``: each clip's first element of ``out`` (host ints);
+    ``out``: flat f32 device tensor.  The host copy of the table is validated here, before upload: channels in
+    1..8, a known format, and each clip's bytes and output range inside ``data`` / ``out``.
+    -> ``(peak_bits, nonfinite)`` uint32-valued int32 device tensors [n_clips]: ``peak_bits.view(torch.float32)``
+    is max |mono sample| over the finite samples, ``nonfinite`` the count of NaN / Inf mono samples."""
+    L.require_device(data, "pcm_decode")
+    dev = data.device
+    _check_flat("data", "pcm_decode", data, torch.uint8, dev)
+    _check_flat("out", "pcm_decode", out, torch.float32, dev)
+    clips = [tuple(int(v) for v in c) for c in clips]
+    out_offsets = [int(o) for o in out_offsets]
+    if len(out_offsets) != len(clips):
+        raise ValueError(f"pcm_decode: {len(out_offsets)} out_offsets for {len(clips)} clips")
+    n = len(clips)
+    peak = torch.empty(n, dtype=torch.int32, device=dev)
+    nonfinite = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return peak, nonfinite
+    table = (L.MiaWavClip * n)()
+    file_bytes = frames_total = 0
+    for i, ((off, frames, ch, fmt), oo) in enumerate(zip(clips, out_offsets)):
+        if not 1 <= ch <= L.WAV_MAX_CHANNELS:
+            raise ValueError(f"pcm_decode: clip {i} has {ch} channels (1..{L.WAV_MAX_CHANNELS})")
+        if not 0 <= fmt < len(L.PCM_BYTES):
+            raise ValueError(f"pcm_decode: clip {i} has unknown format code {fmt}")
+        nb = frames * ch * L.PCM_BYTES[fmt]
+        if frames < 0 or off < 0 or off + nb > data.numel():
+            raise ValueError(f"pcm_decode: clip {i} (byte_off {off}, {frames} frames, {nb} bytes) leaves data "
+                             f"({data.numel()} bytes)")
+        if oo < 0 or oo + frames > out.numel():
+            raise ValueError(f"pcm_decode: clip {i}'s output [{oo}, {oo + frames}) leaves out ({out.numel()})")
+        table[i] = L.MiaWavClip(off, frames, ch, fmt)
+        file_bytes += nb
+        frames_total += frames
+    # the table and the offsets travel as one int64 tensor (a MiaWavClip is three int64 words)
+    host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.int64)
+    words = torch.cat([host, torch.tensor(out_offsets, dtype=torch.int64)]).to(dev)
+    with probe("pcm_decode", 0.0, file_bytes + 4.0 * frames_total):
+        L.check(L.load().mia_pcm_decode(data.data_ptr(), words.data_ptr(), n, words[3 * n:].data_ptr(),
+                                        out.data_ptr(), peak.data_ptr(), nonfinite.data_ptr(), _s()),
+                "mia_pcm_decode")
+    return peak, nonfinite
+
+
+def _check_store(what: str, store: torch.Tensor, offsets: torch.Tensor) -> int:
+    L.require_device(store, what)
+    _check_flat("store", what, store, torch.float32, store.device)
+    _check_flat("offsets", what, offsets, torch.int64, store.device)
+    if offsets.numel() < 1:
+        raise ValueError(f"{what}: offsets must hold n_clips + 1 entries")
+    return offsets.numel() - 1
+
+
+def clip_peak(store: torch.Tensor, offsets: torch.Tensor):
+    """``(peak_bits, nonfinite)`` as ``pcm_decode`` gives them, over clips ``store[offsets[i]:offsets[i+1]]`` of a
+    flat f32 device store (mia_clip_peak; ``offsets`` int64 [n_clips + 1] on the device)."""
+    n = _check_store("clip_peak", store, offsets)
+    peak = torch.empty(n, dtype=torch.int32, device=store.device)
+    nonfinite = torch.empty(n, dtype=torch.int32, device=store.device)
+    with probe("clip_peak", 0.0, 4.0 * store.numel()):
+        L.check(L.load().mia_clip_peak(store.data_ptr(), offsets.data_ptr(), n, peak.data_ptr(),
+                                       nonfinite.data_ptr(), _s()), "mia_clip_peak")
+    return peak, nonfinite
+
+
+def clip_scale(store: torch.Tensor, offsets: torch.Tensor, peak_bits: torch.Tensor) -> torch.Tensor:
+    """In place ``x / peak`` per clip where the peak is > 0 (mia_clip_scale); returns ``store``."""
+    n = _check_store("clip_scale", store, offsets)
+    _check_flat("peak_bits", "clip_scale", peak_bits, torch.int32, store.device)
+    if peak_bits.numel() != n:
+        raise ValueError(f"clip_scale: {peak_bits.numel()} peaks for {n} clips")
+    with probe("clip_scale", 0.0, 8.0 * store.numel()):
+        L.check(L.load().mia_clip_scale(store.data_ptr(), offsets.data_ptr(), n, peak_bits.data_ptr(), _s()),
+                "mia_clip_scale")
+    return store
+
+
 def cast(src: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     out = torch.empty(src.shape, dtype=dtype, device=src.device)
     L.check(L.load().mia_cast(src.data_ptr(), L.dtype_code(src), out.data_ptr(), L.dtype_code(out), src.numel(),

@@ -63,6 +63,14 @@ class MiaMelCfg(C.Structure):
                 ("target_std", f32)]
 
 
+class MiaWavClip(C.Structure):  # include/miaudio_wav.h: one clip of a staged group (24 bytes)
+    _fields_ = [("byte_off", i64), ("frames", i64), ("channels", i32), ("format", i32)]
+
+
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)
+PCM_BYTES = (1, 2, 3, 4, 4, 8)  # bytes per sample of each format
+WAV_MAX_CHANNELS = 8
+
 P = C.POINTER
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -190,6 +198,10 @@ SIGNATURES = {
     "mia_swa_transfer": (C.c_int, [vp, vp, vp, vp, i32, i64, vp]),
     # include/miaudio_data.h
     "mia_crop_gather": (C.c_int, [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp, vp]),
+    # include/miaudio_wav.h
+    "mia_pcm_decode": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, vp]),
+    "mia_clip_peak": (C.c_int, [vp, vp, i64, vp, vp, vp]),
+    "mia_clip_scale": (C.c_int, [vp, vp, i64, vp, vp]),
     "mia_last_error_string": (C.c_char_p, []),
     "mia_device_arch": (C.c_int, [C.c_char_p, i32]),
 }
