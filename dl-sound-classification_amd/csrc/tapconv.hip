@@ -2,6 +2,8 @@
 // conv3: 8x8 taps over the one-channel image) as MFMA tap kernels, gfx950: forward (mia_gemm path 4),
 // weight gradient (path 3), and the conv1 weight gradient fused with the BatchNorm backward reductions
 // (mia_fe_conv1_wgrad_bn, which instantiates the same weight-gradient kernel).  Section comments below.
+#include <cstdlib>
+
 #include "gemm_common.h"
 
 namespace {
@@ -309,6 +311,253 @@ hipError_t tapwgrad_launch(const TapWArgs& r, hipStream_t s) {
   return hipGetLastError();
 }
 
+// -------------------------------------------------------------------------- conv1 wgrad + BN1 backward, wave-private
+// tapwgrad_kernel<bf16, float, 2, 1, 64, true> on another schedule (the default of mia_fe_conv1_wgrad_bn; that
+// kernel is the MIA_CONV1W_V1=1 form).  There, between the cook's wait on a chunk's loads and the next
+// iteration's load_chunk the block has nothing in flight, three block barriers a chunk, and the eight shifted
+// copies of each parity sequence are built with 2-byte LDS reads.  The pixel ownership is already wave-private
+// (thread t cooks pixels (t >> 2) + 64 s2 = k-steps wave + 4 s2, the ones its own wave feeds to the MFMA), so here
+// each wave stages and consumes only its own four k-steps (wave_sync, no block barrier in the loop), two chunks
+// wait in registers (chunk k + 2's loads are issued before chunk k + 1 is cooked), and x goes from the load
+// registers straight to the copies: a k-step reads 96 samples x[2 P0 ..], lane m holds samples 4m .. 4m + 3 as
+// the packed pairs E_m = (x[4m], x[4m+2]) and O_m = (x[4m+1], x[4m+3]) (entries 2m, 2m + 1 of the two parity
+// sequences); copy sh of a sequence (entry i = seq[i + sh], sh = 0 .. 3: a fragment's 8 entries at any offset are
+// two aligned 8-byte reads) takes E_m as dword m (sh 0) / m - 1 (sh 2) and (hi E_m, lo E_{m+1}) as dword m (sh 1)
+// / m - 1 (sh 3).  The 8 copies of a k-step lie 96 B apart: the 32 lanes of a half wave (16 tap offsets x 2
+// parities) read 32 different 8-byte pieces that cover the 64 banks once.
+// Same arithmetic: block z takes chunks z, z + Z, ... in order, wave w the k-steps w, w + 4, w + 8, w + 12 of each
+// into the same four accumulators with the same operand bits (dz = mask & dy, y, bf16(x)); the thread that owns
+// (p mod 64, channel chunk) adds its sdz / sdx / sy terms in increasing pixel order; the folds at the end are
+// tapwgrad_kernel's.
+struct C1WRaw {
+  u32x4 d[4], y[4];
+  float xa[4], xb[4];
+};
+
+__global__ __launch_bounds__(NT, 2) void conv1_wgrad_bn_kernel(TapWArgs g) {
+  constexpr int BP = 256;
+  constexpr int KSB = 1024;            // one k-step's dz (or y) tile: [16 px][32 ch] bf16
+  constexpr int XCB = 96, XKB = 8 * XCB;  // one copy (48 entries), one k-step's 8 copies
+  constexpr int WVB = 8 * KSB + 4 * XKB;  // per wave: dz, y (4 k-steps each), x copies
+  constexpr int REDB = 4 * 32 * 64 * 4;
+  __shared__ __attribute__((aligned(16))) char smem[4 * WVB > REDB ? 4 * WVB : REDB];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int z = blockIdx.x;
+  char* wdz = smem + wave * WVB;
+  char* wy = wdz + 4 * KSB;
+  char* wx = wdz + 8 * KSB;
+  const int CPR = (g.ow + BP - 1) / BP;
+  const int64_t nchunks = (int64_t)g.n * CPR;  // oh == 1: a row is a clip
+  const bf16* dys = reinterpret_cast<const bf16*>(g.dy);
+  const float* xs = reinterpret_cast<const float*>(g.x);
+
+  float bsc[8], bsh[8], bmu[8], bis[8], sdz[8], sdx[8], sy[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int ch = (t & 3) * 8 + i;
+    bsc[i] = g.bsc[ch];
+    bsh[i] = g.bsh[ch];
+    bis[i] = g.binvstd[ch];
+    bmu[i] = g.bmean[ch];
+    sdz[i] = 0.f; sdx[i] = 0.f; sy[i] = 0.f;
+  }
+
+  // x lanes: slot a = (k-step lane >> 4, m = lane & 15), slot b = (k-step (lane >> 3) & 3, m = 16 + (lane & 7));
+  // lanes 32 .. 63 repeat slot b's loads and do not write them
+  const int ksa = lane >> 4, ma = lane & 15, ksb = (lane >> 3) & 3, mb = 16 + (lane & 7);
+  // every load is issued by every lane from a clamped address (chunks past the end repeat the last one) and
+  // masked when cooked: no branch around a load, so the waits on the two register sets stay counted
+  auto load = [&](int64_t c) __attribute__((always_inline)) {
+    C1WRaw R;
+    c = c < nchunks ? c : nchunks - 1;
+    const int64_t b = c / CPR;
+    const int x0 = (int)(c - b * CPR) * BP;
+#pragma unroll
+    for (int s2 = 0; s2 < 4; ++s2) {
+      const int p = 16 * wave + 64 * s2 + (lane >> 2), cc = lane & 3;
+      const bool ok = x0 + p < g.ow;
+      const int64_t off = ok ? (b * g.ow + x0 + p) * 32 + cc * 8 : 0;
+      R.d[s2] = *reinterpret_cast<const u32x4*>(dys + off);
+      R.y[s2] = *reinterpret_cast<const u32x4*>(g.by + off);
+    }
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const float* xb = xs + b * g.wx;
+    const int sa = 2 * (x0 + 16 * (wave + 4 * ksa)) + 4 * ma, sb = 2 * (x0 + 16 * (wave + 4 * ksb)) + 4 * mb;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {  // sample pairs (s, s + 1), s even: inside the clip or outside it (wx is even)
+      const f32x2 va = *reinterpret_cast<const f32x2*>(xb + min(sa + 2 * h, g.wx - 2));
+      const f32x2 vb = *reinterpret_cast<const f32x2*>(xb + min(sb + 2 * h, g.wx - 2));
+      R.xa[2 * h] = va[0]; R.xa[2 * h + 1] = va[1];
+      R.xb[2 * h] = vb[0]; R.xb[2 * h + 1] = vb[1];
+    }
+    return R;
+  };
+  // one slot's 4 samples -> the 8 copies of its k-step; nxt* = E / O of entry pair m + 1
+  auto put_x = [&](int ks, int m, uint32_t e, uint32_t o, uint32_t nxte, uint32_t nxto) __attribute__((always_inline)) {
+    uint32_t* cp = reinterpret_cast<uint32_t*>(wx + ks * XKB);
+    const uint32_t v[2] = {e, o}, s1[2] = {(e >> 16) | (nxte << 16), (o >> 16) | (nxto << 16)};
+#pragma unroll
+    for (int par = 0; par < 2; ++par) {
+      uint32_t* c0 = cp + par * 4 * (XCB / 4);
+      c0[m] = v[par];
+      if (m >= 1) c0[2 * (XCB / 4) + m - 1] = v[par];
+      if (m <= 22) c0[(XCB / 4) + m] = s1[par];
+      if (m >= 1 && m <= 22) c0[3 * (XCB / 4) + m - 1] = s1[par];
+    }
+  };
+  auto cook = [&](const C1WRaw& R, int64_t c) __attribute__((always_inline)) {
+    const int64_t b = c / CPR;
+    const int x0 = (int)(c - b * CPR) * BP;
+    wave_sync();  // the previous chunk's fragment reads are done (common.h)
+#pragma unroll
+    for (int s2 = 0; s2 < 4; ++s2) {
+      uint32_t w4[4] = {0u, 0u, 0u, 0u}, y4[4] = {0u, 0u, 0u, 0u};
+      if (x0 + 16 * wave + 64 * s2 + (lane >> 2) < g.ow) {  // the pixel exists (else zeros, and no sums)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float gv[2], yv[2];
+          gv[0] = __uint_as_float(R.d[s2][i] << 16);
+          gv[1] = __uint_as_float(R.d[s2][i] & 0xffff0000u);
+          yv[0] = __uint_as_float(R.y[s2][i] << 16);
+          yv[1] = __uint_as_float(R.y[s2][i] & 0xffff0000u);
+          uint32_t m = 0;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int ch = 2 * i + h;
+            const bool on = fmaf(yv[h], bsc[ch], bsh[ch]) > 0.f;
+            const float d = on ? gv[h] : 0.f;
+            sdz[ch] += d;
+            sdx[ch] = fmaf(d, (yv[h] - bmu[ch]) * bis[ch], sdx[ch]);
+            sy[ch] += yv[h];
+            m |= on ? (0xffffu << (16 * h)) : 0u;
+          }
+          w4[i] = R.d[s2][i] & m;  // dz = mask * dy exactly (bf16 bits kept or zeroed)
+          y4[i] = R.y[s2][i];
+        }
+      }
+      const int o = s2 * KSB + (lane >> 2) * 64 + (lane & 3) * 16;
+      *reinterpret_cast<u32x4*>(wy + o) = u32x4{y4[0], y4[1], y4[2], y4[3]};
+      *reinterpret_cast<u32x4*>(wdz + o) = u32x4{w4[0], w4[1], w4[2], w4[3]};
+    }
+    // x: zero past the clip's end (tapwgrad_kernel's rule: ix < wx), rounded to bf16 as its (bf16) cast
+    const int sa = 2 * (x0 + 16 * (wave + 4 * ksa)) + 4 * ma, sb = 2 * (x0 + 16 * (wave + 4 * ksb)) + 4 * mb;
+    float xa[4], xb[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      xa[i] = sa + (i & 2) < g.wx ? R.xa[i] : 0.f;
+      xb[i] = sb + (i & 2) < g.wx ? R.xb[i] : 0.f;
+    }
+    const uint32_t ea = pk_bf16(xa[0], xa[2]), oa = pk_bf16(xa[1], xa[3]);
+    const uint32_t eb = pk_bf16(xb[0], xb[2]), ob = pk_bf16(xb[1], xb[3]);
+    // entry pair m + 1: the next lane's, or for m = 15 slot b's first lane of the same k-step
+    // (every lane takes part in every exchange; the choice is made afterwards)
+    const uint32_t nea = __shfl(ea, lane + 1, 64), nea15 = __shfl(eb, 8 * ksa, 64);
+    const uint32_t noa = __shfl(oa, lane + 1, 64), noa15 = __shfl(ob, 8 * ksa, 64);
+    const uint32_t neb = __shfl(eb, lane + 1, 64), nob = __shfl(ob, lane + 1, 64);
+    put_x(ksa, ma, ea, oa, ma < 15 ? nea : nea15, ma < 15 ? noa : noa15);
+    if (lane < 32) put_x(ksb, mb, eb, ob, neb, nob);
+    wave_sync();
+  };
+
+  f32x16 acc[2], acc3[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[j][r] = 0.f; acc3[j][r] = 0.f; }
+  const int i16 = lane & 15, gq = lane >> 4, g2 = lane >> 5;
+  // this lane's tap per n-tile: kx = nt*32 + (lane & 31) -> parity sequence kx & 1, offset kx >> 1; its 8 entries
+  // start at e = 8 g2 + (kx >> 1): copy e & 3, entry e - (e & 3)
+  int xo[2];
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt) {
+    const int kx = nt * 32 + (lane & 31), e = 8 * g2 + (kx >> 1);
+    xo[nt] = ((kx & 1) * 4 + (e & 3)) * XCB + (e - (e & 3)) * 2;
+  }
+  const int ao = (8 * (gq >> 1) + (i16 >> 2)) * 64 + (16 * (gq & 1) + 4 * (i16 & 3)) * 2;
+  auto mma = [&]() __attribute__((always_inline)) {
+    typedef short s16x8 __attribute__((ext_vector_type(8)));
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {  // k-step wave + 4 kk of the chunk
+      const char* p0 = wdz + kk * KSB + ao;
+      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MIA_LDS s16x4*)(p0));
+      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MIA_LDS s16x4*)(p0 + 4 * 64));
+      const s16x8 cc = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      const bf16x8 fa = __builtin_bit_cast(bf16x8, cc);
+      const char* py = wy + kk * KSB + ao;
+      const s16x4 ylo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MIA_LDS s16x4*)(py));
+      const s16x4 yhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MIA_LDS s16x4*)(py + 4 * 64));
+      const s16x8 yc = {ylo[0], ylo[1], ylo[2], ylo[3], yhi[0], yhi[1], yhi[2], yhi[3]};
+      const bf16x8 fy = __builtin_bit_cast(bf16x8, yc);
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const char* src = wx + kk * XKB + xo[nt];
+        const u32x2 q0 = *reinterpret_cast<const u32x2*>(src);
+        const u32x2 q1 = *reinterpret_cast<const u32x2*>(src + 8);
+        const bf16x8 fb = __builtin_bit_cast(bf16x8, u32x4{q0[0], q0[1], q1[0], q1[1]});
+        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc[nt], 0, 0, 0);
+        acc3[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fy, fb, acc3[nt], 0, 0, 0);
+      }
+    }
+  };
+
+  // two chunks wait in registers; whole pairs first with no exit inside a pair (an exit there joins the loop
+  // header in the compiler's flow graph and turns the counted waits into vmcnt(0)), then the odd chunk
+  int64_t c = z;
+  if (c < nchunks) {
+    C1WRaw ra = load(c), rb = load(c + g.Z);
+    for (; c + g.Z < nchunks; c += 2 * (int64_t)g.Z) {
+      cook(ra, c);
+      ra = load(c + 2 * (int64_t)g.Z);
+      mma();
+      cook(rb, c + g.Z);
+      rb = load(c + 3 * (int64_t)g.Z);
+      mma();
+    }
+    if (c < nchunks) {
+      cook(ra, c);
+      mma();
+    }
+  }
+
+  // the folds of tapwgrad_kernel<.., BNB = true>: the 4 waves' partials -> ws[z][2][32][64] (G1 then G3), the
+  // threads' channel sums in thread order -> dbp[z][32][3]
+  float* red = reinterpret_cast<float*>(smem);
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+    __syncthreads();
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = (r & 3) + 8 * (r >> 2) + 4 * g2;
+        red[(wave * 32 + m) * 64 + nt * 32 + (lane & 31)] = which ? acc3[nt][r] : acc[nt][r];
+      }
+    __syncthreads();
+    float* dst = g.ws + ((int64_t)z * 2 + which) * 32 * 64;
+    for (int e = t; e < 32 * 64; e += NT)
+      dst[e] = red[e] + red[2048 + e] + red[4096 + e] + red[6144 + e];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    red[t * 8 + i] = sdz[i];
+    red[2048 + t * 8 + i] = sdx[i];
+    red[4096 + t * 8 + i] = sy[i];
+  }
+  __syncthreads();
+  if (t < 96) {
+    const int q = t / 32, ch = t % 32, cg = ch >> 3, i = ch & 7;
+    float a = 0.f;
+    for (int k = 0; k < NT / 4; ++k) a += red[q * 2048 + (k * 4 + cg) * 8 + i];
+    g.dbp[((int64_t)z * 32 + ch) * 3 + q] = a;
+  }
+}
+
+// A/B switch, read at call time: MIA_CONV1W_V1=1 selects tapwgrad_kernel<bf16, float, 2, 1, 64, true>
+bool conv1w_v1() { const char* e = getenv("MIA_CONV1W_V1"); return e && e[0] == '1'; }
+
 // -------------------------------------------------------------------------- single-channel tap conv (fwd)
 // y[b,oy,ox,n] = sum_{ky,kx} W[n][ky][kx] * X[b, oy+ky, S*ox+kx]  (+ epilogue) for conv1 (1x64,
 // stride 2 over the f32 waveform) and conv3 (8x8 over the 1-channel trunk image): K = 64 taps,
@@ -604,7 +853,13 @@ extern "C" int mia_fe_conv1_wgrad_bn(const float* x, const void* dact, const voi
   double* sums = reinterpret_cast<double*>(g2p + (int64_t)n * (C1_SPLIT * 2 + 64) + 1);  // [160], 8-B aligned below
   sums = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(sums) + 7) & ~uintptr_t(7));
   hipStream_t s = as_stream(stream);
-  hipError_t err = tapwgrad_launch<bf16, float, 2, 1, 64, true>(r, s);
+  hipError_t err;
+  if (conv1w_v1() || (reinterpret_cast<uintptr_t>(x) & 7)) {  // the wave-private form loads x in 8-byte pairs
+    err = tapwgrad_launch<bf16, float, 2, 1, 64, true>(r, s);
+  } else {
+    conv1_wgrad_bn_kernel<<<(unsigned)r.Z, NT, 0, s>>>(r);
+    err = hipGetLastError();
+  }
   if (err != hipSuccess) return mia::fail(-(int)err, "fe_conv1_wgrad_bn launch: %s", hipGetErrorString(err));
   EpiDev e{};
   e.ptr = reinterpret_cast<char*>(g13); e.dtype = MIA_F32; e.act = MIA_ACT_NONE; e.ldc = 2 * 2048; e.alpha = 1.f;
