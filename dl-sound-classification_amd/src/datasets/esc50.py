@@ -18,6 +18,10 @@ onto the GPU:
   over the bundles) and serves the three loaders from it: the pad, the crops and the multi-crop test are one HIP
   gather per batch (``mia_crop_gather``) and no batch touches the host.  Labels and the augmentation pool then come
   from the store as well.
+* ``preprocessing_config.clip_length`` (seconds; off by default) fits every clip of the spectrogram
+  path to one length -- centred trim, wrap or zero padding (``clip_fit``), the reference's
+  src/utils/audio.py::pad_or_trim -- so clips of different lengths batch: ``fit_clip`` in the Dataset on the host
+  path, ``mia_fit_gather`` per batch on the resident store.  Without it the clips are served whole, as before.
 ``SyntheticDataModule`` serves device-resident synthetic clips (benchmarks, plumbing runs).
 """
 from __future__ import annotations
@@ -33,6 +37,44 @@ from torch.utils.data import DataLoader, Dataset
 from torch.utils.data.distributed import DistributedSampler
 
 SR = 44_100
+CLIP_FITS = ("wrap", "zero")
+# the shortest waveform GpuLogMel takes: its reflect padding of n_fft / 2 = 512 samples each side needs T > 512
+# (csrc/logmel.hip, mia_logmel_fwd)
+MIN_LOGMEL_SAMPLES = 513
+
+
+def fit_clip(w: torch.Tensor, length: int, mode: str = "wrap") -> torch.Tensor:
+    """``w`` (..., n) made exactly ``length`` samples long, the rule of the reference's
+    src/utils/audio.py::pad_or_trim (DESIGN.md §20; ``mia_fit_gather`` is the same rule on the resident store):
+    n > length keeps the ``length`` samples from ``(n - length) // 2``; a shorter clip is repeated
+    (``mode="wrap"``: ``out[t] = w[t mod n]``) or followed by +0.0 (``mode="zero"``); an empty clip gives +0.0
+    (the reference would divide by zero).  Samples are copied, never computed with: they keep their bits."""
+    if mode not in CLIP_FITS:
+        raise ValueError(f"fit_clip: mode {mode!r} is not one of {CLIP_FITS}")
+    length, n = int(length), w.shape[-1]
+    if length < 1:
+        raise ValueError(f"fit_clip: length {length} < 1")
+    if n == length:
+        return w
+    if n > length:
+        start = (n - length) // 2
+        return w[..., start:start + length]
+    if n > 0 and mode == "wrap":
+        return w[..., torch.arange(length, device=w.device) % n]
+    out = torch.zeros(*w.shape[:-1], length, dtype=w.dtype, device=w.device)
+    out[..., :n] = w
+    return out
+
+
+def _collate_whole_clips(batch):
+    """The default collate for whole ``"ast"``-mode clips; clips of different lengths cannot be stacked, and the
+    error says which key makes them one length."""
+    lens = sorted({b[0].shape[-1] for b in batch})
+    if len(lens) > 1:
+        raise ValueError(f"the spectrogram path stacks whole clips, but this batch holds clips of {lens[0]} .. "
+                         f"{lens[-1]} samples: set model.dataset_overrides.preprocessing_config.clip_length "
+                         f"(seconds) to fit every clip to one length")
+    return torch.utils.data.default_collate(batch)
 
 
 def _one_hot(y: torch.Tensor, C: int) -> torch.Tensor:
@@ -45,10 +87,11 @@ class ESC50Dataset(Dataset):
     def __init__(self, root, folds: Sequence[int] = (), files: List[Path] | None = None, mode: str = "envnet_v2",
                  pad_crop: bool = False, window_length: float = 5.0, padding_ratio: float = 0.5,
                  training: bool = True, multi_crop_test: bool = False, test_crops: int = 10,
-                 sample_rate: int = SR, store=None):
+                 sample_rate: int = SR, store=None, fit_length: int | None = None, clip_fit: str = "wrap"):
         """``sample_rate``: the rate the window and the padding are counted in.  ``store``: a
         ``resample.ResampledStore`` that already holds every clip at that rate; ``load`` then reads from it
-        instead of the bundle."""
+        instead of the bundle.  ``fit_length``: in ``"ast"`` mode, the samples every clip is fitted to
+        (``fit_clip`` under ``clip_fit``); None serves the clips whole."""
         self.root = Path(root)
         if files is not None:
             self.files = list(files)
@@ -63,6 +106,8 @@ class ESC50Dataset(Dataset):
         self.store = store
         self.pad = int(self.window * padding_ratio)
         self.multi_crop_test, self.test_crops = multi_crop_test, test_crops
+        self.fit_length = int(fit_length) if fit_length is not None and mode == "ast" else None
+        self.clip_fit = clip_fit
 
     def __len__(self):
         return len(self.files)
@@ -72,6 +117,14 @@ class ESC50Dataset(Dataset):
             return self.store.get(self.files[idx])
         b = torch.load(self.files[idx], map_location="cpu", weights_only=True)
         return b["waveform"].float().reshape(1, -1), int(b["label"])
+
+    def clip(self, idx):
+        """``load``, with the clip fitted to ``fit_length`` when one was given (``"ast"`` mode): what
+        ``__getitem__`` serves and the Mixup pool holds."""
+        w, label = self.load(idx)
+        if self.fit_length is not None:
+            w = fit_clip(w, self.fit_length, self.clip_fit)
+        return w, label
 
     def _crop(self, w, start):
         return w[..., start:start + self.window]
@@ -85,7 +138,7 @@ class ESC50Dataset(Dataset):
         return torch.nn.functional.pad(w, (0, self.window - w.shape[-1])) if w.shape[-1] < self.window else w
 
     def __getitem__(self, idx):
-        w, label = self.load(idx)
+        w, label = self.clip(idx)
         if self.mode == "envnet_v2" and not self.pad_crop:
             # BC-mixing path: no T/2 padding, but the reference's random_crop still runs
             # (esc50.py:233-234, preprocessing.py:841-855): a shorter clip (UrbanSound8K's <= 4 s) is
@@ -134,6 +187,7 @@ class ESC50DataModule:
         self.preprocessing_mode = "ast" if is_spectrogram else "envnet_v2"
         self.preprocessing_config = dict(preprocessing_config or {})
         self.num_classes = num_classes
+        self.fit_length, self.clip_fit = self._clip_fitting()
         self.device, self.world, self.rank = torch.device("cpu"), 1, 0
         self._train_set = self._val_set = self._test_set = None
         self._pool = self._pool_labels = None
@@ -152,6 +206,28 @@ class ESC50DataModule:
         Defaults to the data module's own rate, not to the reference's 44100: every configuration that names no
         preprocessing_config.sample_rate stays on the path without resampling."""
         return int(self.preprocessing_config.get("sample_rate", self.sample_rate))
+
+    def _clip_fitting(self):
+        """``(fit_length, clip_fit)`` from ``preprocessing_config.clip_length`` (seconds; absent or null: off, the
+        clips are served whole) and ``.clip_fit``: the spectrogram path's clips fitted to
+        ``int(clip_length * target_rate)`` samples (``fit_clip`` / ``mia_fit_gather``)."""
+        pc = self.preprocessing_config
+        mode = pc.get("clip_fit", "wrap")
+        if mode not in CLIP_FITS:
+            raise ValueError(f"preprocessing_config.clip_fit must be one of {CLIP_FITS}, got {mode!r}")
+        seconds = pc.get("clip_length")
+        if seconds is None:
+            return None, mode
+        if not self.is_spectrogram:
+            raise ValueError("preprocessing_config.clip_length fits the clips of the spectrogram path "
+                             "(is_spectrogram=true); with is_spectrogram=false window_length pads and crops every "
+                             "clip already")
+        length = int(float(seconds) * self.target_rate)
+        if length < MIN_LOGMEL_SAMPLES:
+            raise ValueError(f"preprocessing_config.clip_length={seconds} s is {length} samples at "
+                             f"{self.target_rate} Hz, but the log-mel kernel's reflect padding needs at least "
+                             f"{MIN_LOGMEL_SAMPLES} (more than n_fft / 2 = 512)")
+        return length, mode
 
     @classmethod
     def _fold_error(cls) -> str:
@@ -189,7 +265,8 @@ class ESC50DataModule:
             kw = dict(kw, sample_rate=self.target_rate, store=self._store)
         return ESC50Dataset(self.root, mode=self.preprocessing_mode,
                             window_length=pc.get("window_length", 5.0), padding_ratio=pc.get("padding_ratio", 0.5),
-                            multi_crop_test=pc.get("multi_crop_test", False), test_crops=pc.get("test_crops", 10), **kw)
+                            multi_crop_test=pc.get("multi_crop_test", False), test_crops=pc.get("test_crops", 10),
+                            fit_length=self.fit_length, clip_fit=self.clip_fit, **kw)
 
     def setup(self, stage: str | None = None) -> None:
         if self._train_set is not None:
@@ -244,7 +321,7 @@ class ESC50DataModule:
         if self.resident:
             waves = self._resident_pool_waves(ds)
         elif self.is_spectrogram:
-            waves = torch.stack([ds.load(i)[0][0] for i in range(len(ds))]).to(self.device)
+            waves = torch.stack([ds.clip(i)[0][0] for i in range(len(ds))]).to(self.device)
         else:
             waves = torch.stack([ds.fit_window(ds.load(i)[0])[0] for i in range(len(ds))]).to(self.device)
         self._pool_labels = torch.tensor(self._train_labels, dtype=torch.int64, device=self.device)
@@ -301,17 +378,22 @@ class ESC50DataModule:
     # -------------------------------------------------------------------- loaders
     def _loader(self, ds, shuffle):
         sampler = DistributedSampler(ds, self.world, self.rank, shuffle=shuffle, seed=42) if self.world > 1 else None
+        # whole clips (spectrogram path, no clip_length): the default collate behind a check that names the key
+        collate = _collate_whole_clips if self.is_spectrogram and self.fit_length is None else None
         return DataLoader(ds, batch_size=self.batch_size, shuffle=shuffle and sampler is None, sampler=sampler,
                           num_workers=self.num_workers, pin_memory=self.device.type == "cuda",
-                          persistent_workers=self.num_workers > 0)
+                          persistent_workers=self.num_workers > 0, collate_fn=collate)
 
     def _resident_pool_waves(self, ds):
         """The augmentation pool's waveforms cut from the resident store with the loader's kernel: start 0, no
         padding, one window -- ``fit_window`` (EnvNet) or the whole clip (AST; the clips must be one length, as
-        ``torch.stack`` demands on the host path)."""
+        ``torch.stack`` demands on the host path).  AST with a clip length: the fitted clips (``mia_fit_gather``),
+        as ``ESC50Dataset.clip`` gives them on the host path."""
         st = self._rstore
         sub = st.subset(ds.files)
         window = ds.window
+        if self.is_spectrogram and self.fit_length is not None:
+            return st.fit(sub.to(device=self.device, dtype=torch.int32), self.fit_length, self.clip_fit)
         if self.is_spectrogram:
             lens = {st.lengths_host[i] for i in sub.tolist()}
             if len(lens) != 1:
@@ -329,7 +411,9 @@ class ESC50DataModule:
         st = self._rstore
         kw = dict(batch_size=self.batch_size, window=ds.window, shuffle=training, seed=42, world=self.world,
                   rank=self.rank)
-        if self.is_spectrogram:
+        if self.is_spectrogram and self.fit_length is not None:
+            kw.update(mode="fit", pad=0, window=self.fit_length, fit_mode=self.clip_fit)
+        elif self.is_spectrogram:
             kw.update(mode="whole", pad=0)
         elif training:
             if self._crop_gen is None:
@@ -416,7 +500,9 @@ class SyntheticDataModule(ESC50DataModule):
             from .resample import MAX_CLIPS_PER_LAUNCH, GpuResample
             rs = GpuResample(self.sample_rate, self.target_rate)
             x = torch.cat([rs(x[i:i + MAX_CLIPS_PER_LAUNCH]) for i in range(0, x.shape[0], MAX_CLIPS_PER_LAUNCH)])
-        y = torch.randint(0, self.num_classes, (self.num_clips,), generator=g, device=self.device)
+        if self.fit_length is not None:  # once, in setup: the clips are one length already
+            x = fit_clip(x, self.fit_length, self.clip_fit).contiguous()
+        y =torch.randint(0, self.num_classes, (self.num_clips,), generator=g, device=self.device)
         n = self.num_clips
         nv = max(1, n // 10)
         self._train_set = (x[: n - 2 * nv], y[: n - 2 * nv])

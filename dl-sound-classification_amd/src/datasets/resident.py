@@ -5,6 +5,8 @@ on the device -- and a loader whose batches never touch the host.
 
 * ``ResidentStore``: the flat store, per-clip offsets and labels (device and host), keyed by the bundle's path.
   Built in one pass over the bundles (``build_resident_store``) or from a ``resample.ResampledStore``.
+  ``gather`` cuts pad-and-crop windows out of it, ``fit`` (``mia_fit_gather``) makes whole clips
+  one length for the spectrogram path.
 * ``max_starts`` / ``center_starts`` / ``multi_crop_starts`` / ``draw_starts``: the reference's crop-start rules
   on tensors (CPU or device).
 * ``epoch_indices``: the order of an epoch for this rank.
@@ -110,6 +112,12 @@ class ResidentStore:
         from ..miaudio import kernels as K
         return K.crop_gather(self.data, self.offsets, idx, start, pad, window)
 
+    def fit(self, idx: torch.Tensor, length: int, mode: str = "wrap") -> torch.Tensor:
+        """``(B, length)`` f32: ``K.fit_gather`` on this store (``idx`` int32 [B] on the device) -- every clip
+        trimmed about its centre, wrapped (``mode="wrap"``) or zero-padded (``"zero"``) to ``length`` samples."""
+        from ..miaudio import kernels as K
+        return K.fit_gather(self.data, self.offsets, idx, length, mode)
+
 
 def _check_cap(nbytes: int, max_gib: float):
     if nbytes > float(max_gib) * GIB:
@@ -160,23 +168,24 @@ class _ResidentLoader:
 
     ``subset``: the clip numbers this loader serves (host int64).  ``mode``: ``"random"`` (training crop),
     ``"center"`` (evaluation crop), ``"multi"`` (multi-crop test, ``table`` = the store-wide (N, test_crops) int32
-    device table and ``counts`` its host crop counts) or ``"whole"`` (AST: whole clips of one length).  The epoch's
-    order, clip numbers, labels and starts are formed once in ``__iter__``; a batch is then slices of them and one
-    kernel launch.  ``last_index`` / ``last_start`` hold the most recent batch's clip numbers (int32 [B]) and starts
-    (int32 [B], or [B, ncrop] under "multi")."""
+    device table and ``counts`` its host crop counts), ``"whole"`` (AST: whole clips of one length) or ``"fit"``
+    (AST with ``preprocessing_config.clip_length``: every clip fitted to ``window`` samples by ``store.fit`` under
+    ``fit_mode``; no starts).  The epoch's order, clip numbers, labels and starts are formed once in ``__iter__``; a
+    batch is then slices of them and one kernel launch.  ``last_index`` / ``last_start`` hold the most recent
+    batch's clip numbers (int32 [B]) and starts (int32 [B], or [B, ncrop] under "multi"; None under "fit")."""
 
     def __init__(self, store: ResidentStore, subset: torch.Tensor, batch_size: int, mode: str, pad: int,
                  window: int, shuffle: bool, seed: int = 42, world: int = 1, rank: int = 0,
                  gen: torch.Generator | None = None, table: torch.Tensor | None = None,
-                 counts: torch.Tensor | None = None):
-        if mode not in ("random", "center", "multi", "whole"):
+                 counts: torch.Tensor | None = None, fit_mode: str = "wrap"):
+        if mode not in ("random", "center", "multi", "whole", "fit"):
             raise ValueError(f"_ResidentLoader: mode {mode!r}")
         self.store, self.bs, self.mode, self.shuffle, self.seed = store, int(batch_size), mode, shuffle, seed
         self.world, self.rank, self.epoch, self.gen = world, rank, 0, gen
         self.n = int(subset.numel())
         if self.n < 1:
             raise ValueError("_ResidentLoader: empty subset")
-        self.pad, self.window, self.ncrop = int(pad), int(window), 1
+        self.pad, self.window, self.ncrop, self.fit_mode = int(pad), int(window), 1, fit_mode
         lens = torch.tensor([store.lengths_host[i] for i in subset.tolist()], dtype=torch.int64)
         if mode == "whole":
             if int(lens.min()) != int(lens.max()):
@@ -193,7 +202,7 @@ class _ResidentLoader:
             self.start = center_starts(lens, self.pad, self.window).to(device=dev, dtype=torch.int32)
         elif mode == "whole":
             self.start = torch.zeros(self.n, dtype=torch.int32, device=dev)
-        else:
+        elif mode == "multi":
             c = counts[subset]
             if int(c.min()) != int(c.max()):
                 raise ValueError(f"multi-crop test: the set mixes clips with 1 crop (len + 2 * pad <= window = "
@@ -215,6 +224,13 @@ class _ResidentLoader:
     def __iter__(self):
         order = self._index().to(self.clip.device)
         clip, labels = self.clip[order], self.labels[order]
+        if self.mode == "fit":
+            for i in range(0, order.numel(), self.bs):
+                idx = clip[i:i + self.bs]
+                out = self.store.fit(idx, self.window, self.fit_mode)
+                self.last_index, self.last_start = idx, None
+                yield out.unsqueeze(1), labels[i:i + self.bs]
+            return
         if self.mode == "random":
             start = draw_starts(self.max_start[order], self.gen).to(torch.int32)
         else:

@@ -882,6 +882,35 @@ def crop_gather(store: torch.Tensor, offsets: torch.Tensor, idx: torch.Tensor, s
     return out
 
 
+@torch.no_grad()
+def fit_gather(store: torch.Tensor, offsets: torch.Tensor, idx: torch.Tensor, length: int, mode: str = "wrap",
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """Clip-length fitting from a flat clip store (mia_fit_gather, include/miaudio_data.h): ``store`` f32 [total],
+    ``offsets`` int64 [N + 1], ``idx`` int32 [B] -> f32 [B, length]: a longer clip trimmed about its centre, a
+    shorter one repeated (``mode="wrap"``) or followed by +0.0 (``mode="zero"``).  All on one device."""
+    L.require_device(store, "fit_gather")
+    if mode not in L.FIT_MODES:
+        raise ValueError(f"fit_gather: mode {mode!r} is not one of {sorted(L.FIT_MODES)}")
+    for name, t, dt in (("store", store, torch.float32), ("offsets", offsets, torch.int64),
+                        ("idx", idx, torch.int32)):
+        if t.dtype != dt or t.device != store.device or not t.is_contiguous():
+            raise TypeError(f"fit_gather: {name} must be a contiguous {dt} tensor on {store.device} "
+                            f"(got {t.dtype} on {t.device})")
+    if idx.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError(f"fit_gather: idx {tuple(idx.shape)}, offsets {tuple(offsets.shape)}")
+    B = idx.numel()
+    if out is None:
+        out = torch.empty(B, int(length), dtype=torch.float32, device=store.device)
+    elif (out.dtype != torch.float32 or out.device != store.device or not out.is_contiguous()
+          or out.numel() != B * int(length)):
+        raise TypeError(f"fit_gather: out must be contiguous f32 [{B}, {length}] on {store.device}")
+    with probe("fit_gather", 0.0, 8.0 * out.numel()):
+        L.check(L.load().mia_fit_gather(store.data_ptr(), offsets.data_ptr(), offsets.numel() - 1, idx.data_ptr(),
+                                        B, int(length), L.FIT_MODES[mode], out.data_ptr(), _s()),
+                "mia_fit_gather")
+    return out
+
+
 # ------------------------------------------------------------------------------------ WAV ingestion
 def _check_flat(name: str, what: str, t: torch.Tensor, dt, device):
     if t.dtype != dt or t.device != device or not t.is_contiguous() or t.dim() != 1:

@@ -69,6 +69,7 @@ class MiaWavClip(C.Structure):  # include/miaudio_wav.h: one clip of a staged gr
 
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)
 PCM_BYTES = (1, 2, 3, 4, 4, 8)  # bytes per sample of each format
+FIT_MODES = {"wrap": 0, "zero": 1}  # MIA_FIT_WRAP, MIA_FIT_ZERO (include/miaudio_data.h)
 WAV_MAX_CHANNELS = 8
 
 P = C.POINTER
@@ -198,6 +199,7 @@ SIGNATURES = {
     "mia_swa_transfer": (C.c_int, [vp, vp, vp, vp, i32, i64, vp]),
     # include/miaudio_data.h
     "mia_crop_gather": (C.c_int, [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "mia_fit_gather": (C.c_int, [vp, vp, i64, vp, i32, i32, i32, vp, vp]),
     # include/miaudio_wav.h
     "mia_pcm_decode": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, vp]),
     "mia_clip_peak": (C.c_int, [vp, vp, i64, vp, vp, vp]),
