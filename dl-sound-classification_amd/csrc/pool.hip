@@ -7,6 +7,7 @@
 // PyTorch CPU kernel.
 #include <cstdlib>
 
+#include "../../include/miaudio_pool.h"
 #include "channel_partials.h"
 
 namespace {
@@ -429,7 +430,8 @@ __global__ __launch_bounds__(NT) void pool_bwd_kernel(const void* __restrict__ d
 // Sparse BN reductions of the pooled backward: only the argmax position of each pooled cell carries
 // a gradient, so dbeta = sum g and dgamma = sum g * xhat are gathered per pooled cell (one thread =
 // one (pooled cell, 8-channel group)) without touching the other kh*kw - 1 pixels of the window.
-// gm[cell][c] (f32, NHWC cells) keeps the ReLU-masked gradient at the argmax for the dense pass.
+// gm[cell][c] (NHWC cells; f32, or x's dtype: each entry is a dout value or 0, so a bf16 gm converts back to the
+// same float) keeps the ReLU-masked gradient at the argmax for the dense pass.
 // win (optional, NHWC cells, x's dtype): the raw winner value of each cell saved by the forward
 // (pool_raw_stats); when given, x is not gathered at all -- a contiguous read replaces kh*kw-strided
 // 2-byte gathers that each touch a separate cache line.
@@ -442,7 +444,7 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_kernel(const void* __restr
                                                              const float* __restrict__ shift,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ invstd,
-                                                             float* __restrict__ gm,
+                                                             void* __restrict__ gm, int gdt,
                                                              float* __restrict__ partial) {
   const int OH = H / kh, OW = W / kw, G = C / 8;
   const int t = threadIdx.x;
@@ -484,9 +486,7 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_kernel(const void* __restr
       s1[i] += g;
       s2[i] = fmaf(g, (xv[i] - mu[i]) * is[i], s2[i]);
     }
-    float4* gq = reinterpret_cast<float4*>(gm + (int64_t)cell * C + cg * 8);
-    gq[0] = make_float4(gv[0], gv[1], gv[2], gv[3]);
-    gq[1] = make_float4(gv[4], gv[5], gv[6], gv[7]);
+    store8(gm, gdt, (int64_t)cell * C + cg * 8, gv);  // bf16 gm: gv is a bf16 value or 0, the rounding is exact
   }
   // cp_fold<2> written out: this kernel is the MIA_POOL_V1 oracle of pool_bwd_sparse_tr_kernel
   // (tests/test_gpu_pool_forms.py) and stays independent of the shared fold that kernel uses
@@ -500,6 +500,89 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_kernel(const void* __restr
     for (int r2 = 0; r2 < rslots; ++r2) acc += red[(r2 * G + g2) * 16 + qq * 8 + ci];
     partial[((int64_t)blockIdx.x * C + c) * 2 + qq] = acc;
   }
+}
+
+// Eight consecutive elements of a DT-typed array as raw 16-B vectors (bf16: one, f32: two) and their floats: the
+// load and the conversion apart, so that a kernel can issue the loads of several iterations before the first use.
+template <int DT>
+struct Raw8 {
+  uint4 v[DT == MIA_BF16 ? 1 : 2];
+  __device__ __forceinline__ void load(const void* p, int64_t off) {
+    const uint4* q = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(p) + off * (DT == MIA_BF16 ? 2 : 4));
+    v[0] = q[0];
+    if constexpr (DT != MIA_BF16) v[1] = q[1];
+  }
+  __device__ __forceinline__ void unpack(float (&f)[8]) const {
+    if constexpr (DT == MIA_BF16) {
+      const uint32_t w[4] = {v[0].x, v[0].y, v[0].z, v[0].w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
+    } else {
+      const uint32_t w[8] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) f[i] = __uint_as_float(w[i]);
+    }
+  }
+};
+
+#ifndef PG_DEPTH
+// loop iterations whose loads pool_bwd_sparse_ra_kernel issues before the first use.  In the B = 256 EnvNet step the
+// three NHWC trunk launches take 21.9-23.8 / 23.0-26.3 / 25.1-27.7 / 27.7-30.0 us at 1 / 2 / 4 / 8:
+// with 16-B loads the kernel runs at the rate its bytes arrive, and reading ahead only costs registers
+#define PG_DEPTH 1
+#endif
+// pool_bwd_sparse_kernel for an NHWC pooled gradient with the winners saved (win): same grid, same cell ->
+// (block, thread) map, the same per-thread order of adds and the same fold, so gm and partial come out bit for bit.
+// Only how the bytes arrive changes: no division decodes the cell (dout and win share gm's offset), a thread's eight
+// channels of dout are one 16-B load like win's (bf16; the earlier form issued eight 2-byte loads through
+// out_index / ld_elem), and the loads of D consecutive loop iterations are issued before the first use -- clamped
+// to the last cell, never under a branch.
+template <int DT, int GDT, int D>
+__global__ __launch_bounds__(NT) void pool_bwd_sparse_ra_kernel(const void* __restrict__ dout,
+                                                                const void* __restrict__ win, int cells, int C,
+                                                                const float* __restrict__ scale,
+                                                                const float* __restrict__ shift,
+                                                                const float* __restrict__ mean,
+                                                                const float* __restrict__ invstd,
+                                                                void* __restrict__ gm, float* __restrict__ partial) {
+  const int G = C / 8;
+  const int t = threadIdx.x;
+  const int cg = t % G, rs = t / G, rslots = NT / G;
+  float sc[8], sh[8], mu[8], is[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    sc[i] = scale[cg * 8 + i]; sh[i] = shift[cg * 8 + i]; mu[i] = mean[cg * 8 + i]; is[i] = invstd[cg * 8 + i];
+  }
+  float s1[8] = {0}, s2[8] = {0};
+  const int stride = gridDim.x * rslots;  // cells + D * stride < 2^31 (checked by the launcher)
+  for (int cell0 = blockIdx.x * rslots + rs; cell0 < cells; cell0 += D * stride) {
+    Raw8<DT> wr[D], dr[D];
+#pragma unroll
+    for (int v = 0; v < D; ++v) {
+      const int64_t off = (int64_t)min(cell0 + v * stride, cells - 1) * C + cg * 8;
+      wr[v].load(win, off);
+      dr[v].load(dout, off);
+    }
+#pragma unroll
+    for (int v = 0; v < D; ++v) {
+      // no branch around the arithmetic: hipcc sinks an iteration's loads into a branch that holds their only
+      // uses, next to the first use, and one iteration is in flight again.  Past the last cell the sums keep
+      // their value.
+      const bool live = cell0 + v * stride < cells;
+      float xv[8], dv[8], gv[8];
+      wr[v].unpack(xv);
+      dr[v].unpack(dv);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float g = fmaf(xv[i], sc[i], sh[i]) > 0.f ? dv[i] : 0.f;
+        gv[i] = g;
+        s1[i] = live ? s1[i] + g : s1[i];
+        s2[i] = live ? fmaf(g, (xv[i] - mu[i]) * is[i], s2[i]) : s2[i];
+      }
+      if (live) store8(gm, GDT, (int64_t)(cell0 + v * stride) * C + cg * 8, gv);
+    }
+  }
+  cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);
 }
 
 // pool_bwd_sparse_kernel for a channel-major pooled gradient (layouts 1 and 2: dout[(b * C + c) * S + p],
@@ -519,7 +602,8 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_tr_kernel(const void* __re
                                                                 const float* __restrict__ shift,
                                                                 const float* __restrict__ mean,
                                                                 const float* __restrict__ invstd,
-                                                                float* __restrict__ gm, float* __restrict__ partial) {
+                                                                void* __restrict__ gm, int gdt,
+                                                                float* __restrict__ partial) {
   const int OW = W / kw, S = (H / kh) * OW, G = C / 8;
   const int t = threadIdx.x;
   const int lb = xcd_block_id();  // the logical block: blocks whose cells share dout lines on one L2
@@ -602,9 +686,7 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_tr_kernel(const void* __re
         s1[i] += g;
         s2[i] = fmaf(g, (xv[i] - mu[i]) * is[i], s2[i]);
       }
-      float4* gq = reinterpret_cast<float4*>(gm + cell * C + cg * 8);
-      gq[0] = make_float4(gv[0], gv[1], gv[2], gv[3]);
-      gq[1] = make_float4(gv[4], gv[5], gv[6], gv[7]);
+      store8(gm, gdt, cell * C + cg * 8, gv);
     }
     __syncthreads();  // also the barrier between the last tile reads and the fold's writes to red
   }
@@ -620,7 +702,8 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_tr_kernel(const void* __re
 // 8 consecutive pixels of one row, which always fall in ONE pooled cell, so the cell's argmax bytes
 // and masked gradient (40 B) are read once per 8 pixels instead of once per pixel, and the index
 // math runs once per octet.  All 8 pixel loads are issued before any use.
-__global__ __launch_bounds__(NT) void pool_bn_bwd_apply_oct_kernel(const float* __restrict__ gm,
+template <int GDT>  // gm's dtype
+__global__ __launch_bounds__(NT) void pool_bn_bwd_apply_oct_kernel(const void* __restrict__ gm,
                                                                    const uint8_t* __restrict__ argmax,
                                                                    const bf16* __restrict__ x, int n, int H, int W,
                                                                    int C, int kh, int kw, FastDiv dNO, FastDiv dH,
@@ -657,8 +740,8 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_oct_kernel(const float* 
     const bool cell = oy < OH && ox < OW;
     const int64_t coff = cell ? (((int64_t)b * OH + oy) * OW + ox) * C + cg * 8 : 0;
     const uint2 am = *reinterpret_cast<const uint2*>(argmax + coff);
-    const float4 g0 = reinterpret_cast<const float4*>(gm + coff)[0];
-    const float4 g1 = reinterpret_cast<const float4*>(gm + coff)[1];
+    Raw8<GDT> gr;
+    gr.load(gm, coff);
     const int64_t xoff = ((int64_t)rowi * W + ix0) * C + cg * 8;
     uint4 xr[8];
 #pragma unroll
@@ -666,7 +749,8 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_oct_kernel(const float* 
       const int64_t o = ix0 + j < W ? xoff + (int64_t)j * C : xoff;
       xr[j] = *reinterpret_cast<const uint4*>(x + o);
     }
-    const float gv[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+    float gv[8];
+    gr.unpack(gv);
     const int pos0 = (iy - oy * kh) * kw + (ix0 - ox * kw);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -701,8 +785,8 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_oct_kernel(const float* 
 // thread-iteration, all loads issued before any use.  EnvNet block 0 (B = 256, 50 x 846 x 32, (5, 3)):
 // 0.447 ms per pixel -> 0.345 ms per run (4.25 TB/s on x + dx + gm); folding the five per-channel
 // constants into three (occupancy 4 -> 5) measured no faster.
-template <int KW, int RU>
-__global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const float* __restrict__ gm,
+template <int KW, int RU, int GDT>
+__global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const void* __restrict__ gm,
                                                                    const uint8_t* __restrict__ argmax,
                                                                    const bf16* __restrict__ x, int n, int H, int W,
                                                                    int C, int kh, FastDiv dNR, FastDiv dH, FastDiv dG,
@@ -732,7 +816,7 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const float* 
   for (int u0 = blockIdx.x * NT + t; u0 < units; u0 += RU * stride) {
     uint4 xr[RU][KW];
     uint2 am[RU];
-    float4 g0[RU], g1[RU];
+    Raw8<GDT> gr[RU];
     int64_t xoff[RU];
     int pos0[RU], ix0[RU];
 #pragma unroll
@@ -749,8 +833,7 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const float* 
       const int64_t coff = cell ? (((int64_t)b * OH + oy) * OW + run) * C + cg * 8 : 0;
       pos0[v] = cell ? (iy - oy * kh) * KW : -256;
       am[v] = *reinterpret_cast<const uint2*>(argmax + coff);
-      g0[v] = reinterpret_cast<const float4*>(gm + coff)[0];
-      g1[v] = reinterpret_cast<const float4*>(gm + coff)[1];
+      gr[v].load(gm, coff);
       xoff[v] = ((int64_t)rowi * W + ix0[v]) * C + cg * 8;
 #pragma unroll
       for (int j = 0; j < KW; ++j) {
@@ -761,7 +844,8 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const float* 
 #pragma unroll
     for (int v = 0; v < RU; ++v) {
       if (u0 + v * stride >= units) break;
-      const float gv[8] = {g0[v].x, g0[v].y, g0[v].z, g0[v].w, g1[v].x, g1[v].y, g1[v].z, g1[v].w};
+      float gv[8];
+      gr[v].unpack(gv);
 #pragma unroll
       for (int j = 0; j < KW; ++j) {
         if (ix0[v] + j >= W) break;
@@ -798,7 +882,8 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const float* 
 #ifndef PB_RUNS
 #define PB_RUNS 1  // runs per thread-iteration: 1, 2, 3 measured equal within 5% (block 0: 0.34-0.36 ms)
 #endif
-__global__ __launch_bounds__(NT) void pool_bn_bwd_apply_kernel(const float* __restrict__ gm,
+template <int GDT>
+__global__ __launch_bounds__(NT) void pool_bn_bwd_apply_kernel(const void* __restrict__ gm,
                                                                const uint8_t* __restrict__ argmax,
                                                                const void* __restrict__ x, int dtype, int n, int H,
                                                                int W, int C, int kh, int kw, FastDiv dW, FastDiv dH,
@@ -828,7 +913,7 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_kernel(const float* __re
   for (int r0 = blockIdx.x * rslots + rs; r0 < P; r0 += PB_UNROLL * stride) {
     float xv[PB_UNROLL][8];
     uint2 am[PB_UNROLL];
-    float4 g0[PB_UNROLL], g1[PB_UNROLL];
+    Raw8<GDT> gr[PB_UNROLL];
 #pragma unroll
     for (int u = 0; u < PB_UNROLL; ++u) {
       const int r = min(r0 + u * stride, P - 1);
@@ -838,8 +923,7 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_kernel(const float* __re
       const int oy = min((int)fdiv(iy, dkh), OH - 1), ox = min((int)fdiv(ix, dkw), OW - 1);
       const int64_t coff = (((int64_t)b * OH + oy) * OW + ox) * C + cg * 8;
       am[u] = *reinterpret_cast<const uint2*>(argmax + coff);
-      g0[u] = reinterpret_cast<const float4*>(gm + coff)[0];
-      g1[u] = reinterpret_cast<const float4*>(gm + coff)[1];
+      gr[u].load(gm, coff);
     }
 #pragma unroll
     for (int u = 0; u < PB_UNROLL; ++u) {
@@ -849,7 +933,8 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_kernel(const float* __re
       const int iy = q - (int)fdiv(q, dH) * H;
       const int oy = (int)fdiv(iy, dkh), ox = (int)fdiv(ix, dkw);
       const int pos = oy < OH && ox < OW ? (iy - oy * kh) * kw + (ix - ox * kw) : -1;
-      const float gv[8] = {g0[u].x, g0[u].y, g0[u].z, g0[u].w, g1[u].x, g1[u].y, g1[u].z, g1[u].w};
+      float gv[8];
+      gr[u].unpack(gv);
       float g[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -977,32 +1062,61 @@ extern "C" int mia_pool_bwd_bn_relu_reduce(const void* dout, int32_t out_layout,
   return 0;
 }
 
-extern "C" int mia_pool_bwd_gather(const void* dout, int32_t out_layout, const uint8_t* argmax, const void* x,
-                                   const void* win, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh, int32_t kw,
-                                   const float* scale, const float* shift, const float* mean, const float* invstd,
-                                   float* gm, float* dgamma, float* dbeta, void* partial, mia_stream_t stream) {
+// MIA_POOL_GRID=n, read at call time: at most n blocks for mia_pool_bwd_gather's main kernel, whichever form runs
+// (it only lowers the grid; the tests use it to make a thread walk many cells at small shapes)
+static int pool_grid_cap(int nb) {
+  const char* e = getenv("MIA_POOL_GRID");
+  const int cap = e ? atoi(e) : 0;
+  return cap > 0 ? std::min(nb, cap) : nb;
+}
+
+extern "C" int mia_pool_bwd_gather_ex(const void* dout, int32_t out_layout, const uint8_t* argmax, const void* x,
+                                      const void* win, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c,
+                                      int32_t kh, int32_t kw, const float* scale, const float* shift,
+                                      const float* mean, const float* invstd, void* gm, int32_t gm_dtype,
+                                      float* dgamma, float* dbeta, void* partial, mia_stream_t stream) {
   MIA_CHECK_ARG(dout && argmax && x && scale && shift && mean && invstd && gm && dgamma && dbeta && partial,
                 "pool_bwd_gather: null pointer");
   MIA_CHECK_ARG(c % 8 == 0 && c >= 8 && (NT % (c / 8)) == 0, "pool_bwd_gather: channels");
   MIA_CHECK_ARG((int64_t)n * h * w < (1ll << 31), "pool_bwd_gather: too many pixels for 32-bit indexing");
+  // a cell's eight channels are one 16-B (bf16 gm) or two 16-B (f32 gm) stores: 16-byte alignment either way
   MIA_CHECK_ARG(h >= kh && w >= kw && kh * kw <= 256 && (reinterpret_cast<uintptr_t>(gm) & 15) == 0,
                 "pool_bwd_gather: bad geometry / alignment");
+  MIA_CHECK_ARG(gm_dtype == MIA_F32 || (gm_dtype == MIA_BF16 && dtype == MIA_BF16),
+                "pool_bwd_gather: gm is f32, or bf16 beside bf16 activations (gm dtype %d, dtype %d)", gm_dtype, dtype);
   const int rslots = NT / (c / 8);
   const int64_t cells = (int64_t)n * (h / kh) * (w / kw);
-  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(cells, (int64_t)rslots * 2), CP_MAXBLK));
+  const int nb = pool_grid_cap((int)std::max<int64_t>(1, std::min<int64_t>(cdiv(cells, (int64_t)rslots * 2), CP_MAXBLK)));
   hipStream_t s = as_stream(stream);
   MIA_CHECK_ARG(!win || (reinterpret_cast<uintptr_t>(win) & 15) == 0, "pool_bwd_gather: win alignment");
+  const bool v1 = pool_v1();
+  const bool chmajor = out_layout == 2 || (out_layout == 1 && h / kh == 1);
   // the staged form from 16 cells a block iteration on (channel runs of 32 B and more; C <= 128): the frontend's
   // gradient (C = 64) went 50 -> 33 us, the last trunk pool's (C = 256, 8 cells, 16-B runs) measured 87 -> 89 us
-  if (!pool_v1() && (out_layout == 2 || (out_layout == 1 && h / kh == 1)) && rslots >= 16 &&
-      cells < (1ll << 31) - 1024) {
+  if (!v1 && chmajor && rslots >= 16 && cells < (1ll << 31) - 1024) {
     int lg_nch = 0;
     while ((4 << lg_nch) < rslots) ++lg_nch;  // rslots / 4 pieces per channel (rslots divides 256: a power of two)
     pool_bwd_sparse_tr_kernel<<<nb, NT, 0, s>>>(dout, argmax, x, win, dtype, (int)cells, h, w, c, kh, kw, lg_nch, scale,
-                                                shift, mean, invstd, gm, (float*)partial);
+                                                shift, mean, invstd, gm, gm_dtype, (float*)partial);
+  } else if (!v1 && win && out_layout == 0 && (dtype == MIA_BF16 || dtype == MIA_F32) &&
+             (reinterpret_cast<uintptr_t>(dout) & 15) == 0 && cells + (int64_t)PG_DEPTH * nb * rslots < (1ll << 31)) {
+    // NHWC dout and saved winners: 16-B loads, PG_DEPTH iterations ahead.  (Channel-major dout with 8 cells a block
+    // iteration, the last trunk pool: this form with element loads 1 / 2 / 4 / 8 iterations ahead measured 78 ->
+    // 78-85 / 82-89 / 86-89 / 106-132 us: not kept, it stays on pool_bwd_sparse_kernel.)
+    float* part = (float*)partial;
+    const int nc = (int)cells;
+    if (dtype == MIA_F32)
+      pool_bwd_sparse_ra_kernel<MIA_F32, MIA_F32, PG_DEPTH><<<nb, NT, 0, s>>>(dout, win, nc, c, scale, shift, mean,
+                                                                              invstd, gm, part);
+    else if (gm_dtype == MIA_F32)
+      pool_bwd_sparse_ra_kernel<MIA_BF16, MIA_F32, PG_DEPTH><<<nb, NT, 0, s>>>(dout, win, nc, c, scale, shift, mean,
+                                                                               invstd, gm, part);
+    else
+      pool_bwd_sparse_ra_kernel<MIA_BF16, MIA_BF16, PG_DEPTH><<<nb, NT, 0, s>>>(dout, win, nc, c, scale, shift, mean,
+                                                                                invstd, gm, part);
   } else {
     pool_bwd_sparse_kernel<<<nb, NT, 0, s>>>(dout, out_layout, argmax, x, win, dtype, n, h, w, c, kh, kw, scale, shift,
-                                             mean, invstd, gm, (float*)partial);
+                                             mean, invstd, gm, gm_dtype, (float*)partial);
   }
   MIA_LAUNCH_CHECK("pool_bwd_gather");
   cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum g*/ dbeta,
@@ -1011,27 +1125,29 @@ extern "C" int mia_pool_bwd_gather(const void* dout, int32_t out_layout, const u
   return 0;
 }
 
-extern "C" int mia_pool_bn_relu_bwd_apply(const float* gm, const uint8_t* argmax, const void* x, int32_t dtype,
-                                          int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh, int32_t kw,
-                                          const float* gamma, const float* mean, const float* invstd,
-                                          const float* dgamma, const float* dbeta, void* dx, float* dbias,
-                                          void* partial, mia_stream_t stream) {
-  MIA_CHECK_ARG(gm && argmax && x && mean && invstd && dgamma && dbeta && dx, "pool_bn_bwd_apply: null pointer");
-  MIA_CHECK_ARG(!dbias || partial, "pool_bn_bwd_apply: dbias needs the partial workspace");
-  MIA_CHECK_ARG(c % 8 == 0 && c >= 8 && (NT % (c / 8)) == 0, "pool_bn_bwd_apply: channels");
-  MIA_CHECK_ARG((int64_t)n * h * w < (1ll << 31), "pool_bn_bwd_apply: too many pixels for 32-bit indexing");
-  MIA_CHECK_ARG(h >= kh && w >= kw && kh * kw <= 256, "pool_bn_bwd_apply: bad geometry");
+extern "C" int mia_pool_bwd_gather(const void* dout, int32_t out_layout, const uint8_t* argmax, const void* x,
+                                   const void* win, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh, int32_t kw,
+                                   const float* scale, const float* shift, const float* mean, const float* invstd,
+                                   float* gm, float* dgamma, float* dbeta, void* partial, mia_stream_t stream) {
+  return mia_pool_bwd_gather_ex(dout, out_layout, argmax, x, win, dtype, n, h, w, c, kh, kw, scale, shift, mean, invstd,
+                                gm, MIA_F32, dgamma, dbeta, partial, stream);
+}
+
+template <int GDT>
+static int pool_bn_bwd_apply_launch(const void* gm, const uint8_t* argmax, const void* x, int32_t dtype, int32_t n,
+                                    int32_t h, int32_t w, int32_t c, int32_t kh, int32_t kw, const float* gamma,
+                                    const float* mean, const float* invstd, const float* dgamma, const float* dbeta,
+                                    void* dx, float* dbias, void* partial, hipStream_t s) {
   const int rslots = NT / (c / 8);
   const int64_t P = (int64_t)n * h * w;
-  hipStream_t s = as_stream(stream);
   const int64_t units = (int64_t)n * h * ((w + 7) / 8) * (c / 8);
   if (kw % 8 == 0 && dtype == MIA_BF16 && units < (1ll << 31) &&
       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(units, NT), CP_MAXBLK));
-    pool_bn_bwd_apply_oct_kernel<<<nb, NT, 0, s>>>(gm, argmax, reinterpret_cast<const bf16*>(x), n, h, w, c, kh, kw,
-                                                   make_fastdiv((w + 7) / 8), make_fastdiv(h), make_fastdiv(c / 8),
-                                                   gamma, mean, invstd, dgamma, dbeta, reinterpret_cast<bf16*>(dx),
-                                                   dbias ? (float*)partial : nullptr);
+    pool_bn_bwd_apply_oct_kernel<GDT><<<nb, NT, 0, s>>>(gm, argmax, reinterpret_cast<const bf16*>(x), n, h, w, c, kh, kw,
+                                                        make_fastdiv((w + 7) / 8), make_fastdiv(h), make_fastdiv(c / 8),
+                                                        gamma, mean, invstd, dgamma, dbeta, reinterpret_cast<bf16*>(dx),
+                                                        dbias ? (float*)partial : nullptr);
     MIA_LAUNCH_CHECK("pool_bn_bwd_apply");
     if (dbias) {
       cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
@@ -1050,14 +1166,14 @@ extern "C" int mia_pool_bn_relu_bwd_apply(const float* gm, const uint8_t* argmax
     const bf16* xb = reinterpret_cast<const bf16*>(x);
     bf16* dxb = reinterpret_cast<bf16*>(dx);
     if (kw == 2)
-      pool_bn_bwd_apply_run_kernel<2, RU><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma, mean,
-                                                            invstd, dgamma, dbeta, dxb, part);
+      pool_bn_bwd_apply_run_kernel<2, RU, GDT><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma,
+                                                                 mean, invstd, dgamma, dbeta, dxb, part);
     else if (kw == 3)
-      pool_bn_bwd_apply_run_kernel<3, RU><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma, mean,
-                                                            invstd, dgamma, dbeta, dxb, part);
+      pool_bn_bwd_apply_run_kernel<3, RU, GDT><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma,
+                                                                 mean, invstd, dgamma, dbeta, dxb, part);
     else
-      pool_bn_bwd_apply_run_kernel<4, RU><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma, mean,
-                                                            invstd, dgamma, dbeta, dxb, part);
+      pool_bn_bwd_apply_run_kernel<4, RU, GDT><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma,
+                                                                 mean, invstd, dgamma, dbeta, dxb, part);
     MIA_LAUNCH_CHECK("pool_bn_bwd_apply_run");
     if (dbias) {
       cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
@@ -1066,15 +1182,45 @@ extern "C" int mia_pool_bn_relu_bwd_apply(const float* gm, const uint8_t* argmax
     return 0;
   }
   const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(P, (int64_t)rslots * 8), CP_MAXBLK));
-  pool_bn_bwd_apply_kernel<<<nb, NT, 0, s>>>(gm, argmax, x, dtype, n, h, w, c, kh, kw, make_fastdiv(w), make_fastdiv(h),
-                                             make_fastdiv(kw), make_fastdiv(kh), gamma, mean, invstd, dgamma,
-                                             dbeta, dx, dbias ? (float*)partial : nullptr);
+  pool_bn_bwd_apply_kernel<GDT><<<nb, NT, 0, s>>>(gm, argmax, x, dtype, n, h, w, c, kh, kw, make_fastdiv(w),
+                                                  make_fastdiv(h), make_fastdiv(kw), make_fastdiv(kh), gamma, mean,
+                                                  invstd, dgamma, dbeta, dx, dbias ? (float*)partial : nullptr);
   MIA_LAUNCH_CHECK("pool_bn_bwd_apply");
   if (dbias) {
     cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
     MIA_LAUNCH_CHECK("pool_bn_bwd_apply_final");
   }
   return 0;
+}
+
+extern "C" int mia_pool_bn_relu_bwd_apply_ex(const void* gm, int32_t gm_dtype, const uint8_t* argmax, const void* x,
+                                             int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh,
+                                             int32_t kw, const float* gamma, const float* mean, const float* invstd,
+                                             const float* dgamma, const float* dbeta, void* dx, float* dbias,
+                                             void* partial, mia_stream_t stream) {
+  MIA_CHECK_ARG(gm && argmax && x && mean && invstd && dgamma && dbeta && dx, "pool_bn_bwd_apply: null pointer");
+  MIA_CHECK_ARG(!dbias || partial, "pool_bn_bwd_apply: dbias needs the partial workspace");
+  MIA_CHECK_ARG(c % 8 == 0 && c >= 8 && (NT % (c / 8)) == 0, "pool_bn_bwd_apply: channels");
+  MIA_CHECK_ARG((int64_t)n * h * w < (1ll << 31), "pool_bn_bwd_apply: too many pixels for 32-bit indexing");
+  MIA_CHECK_ARG(h >= kh && w >= kw && kh * kw <= 256, "pool_bn_bwd_apply: bad geometry");
+  MIA_CHECK_ARG(gm_dtype == MIA_F32 || gm_dtype == MIA_BF16, "pool_bn_bwd_apply: gm dtype %d", gm_dtype);
+  // a cell's eight channels are read as 16-B vectors (one of bf16, two of f32)
+  MIA_CHECK_ARG((reinterpret_cast<uintptr_t>(gm) & 15) == 0, "pool_bn_bwd_apply: gm alignment");
+  hipStream_t s = as_stream(stream);
+  if (gm_dtype == MIA_BF16)
+    return pool_bn_bwd_apply_launch<MIA_BF16>(gm, argmax, x, dtype, n, h, w, c, kh, kw, gamma, mean, invstd, dgamma,
+                                              dbeta, dx, dbias, partial, s);
+  return pool_bn_bwd_apply_launch<MIA_F32>(gm, argmax, x, dtype, n, h, w, c, kh, kw, gamma, mean, invstd, dgamma, dbeta,
+                                           dx, dbias, partial, s);
+}
+
+extern "C" int mia_pool_bn_relu_bwd_apply(const float* gm, const uint8_t* argmax, const void* x, int32_t dtype,
+                                          int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh, int32_t kw,
+                                          const float* gamma, const float* mean, const float* invstd,
+                                          const float* dgamma, const float* dbeta, void* dx, float* dbias,
+                                          void* partial, mia_stream_t stream) {
+  return mia_pool_bn_relu_bwd_apply_ex(gm, MIA_F32, argmax, x, dtype, n, h, w, c, kh, kw, gamma, mean, invstd, dgamma,
+                                       dbeta, dx, dbias, partial, stream);
 }
 
 extern "C" int mia_col2im_rows(const float* p, int32_t n, int32_t ph, int32_t w, int32_t kh, void* out, int32_t dtype,

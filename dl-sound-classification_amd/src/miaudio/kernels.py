@@ -374,32 +374,38 @@ def bn_relu_bwd_apply(dact, x, dx, P, C, gamma, bn: BNState, dgamma, dbeta, dbia
                                       ws.data_ptr(), _s()), "mia_bn_relu_bwd_apply")
 
 
-def pool_bwd_gather(dout, out_layout, argmax, x, n, h, w, c, kh, kw, bn: BNState, win=None):
+def pool_bwd_gather(dout, out_layout, argmax, x, n, h, w, c, kh, kw, bn: BNState, win=None, gm_dtype=None):
     """Sparse half of the pooled backward: (gm, dgamma, dbeta); gm = ReLU-masked gradient at each
-    pooled cell's argmax, f32 (n, h//kh, w//kw, c).  ``win``: the raw winner values the forward
-    saved (pool_raw_stats), read instead of gathering x at the argmax positions."""
+    pooled cell's argmax, (n, h//kh, w//kw, c).  ``win``: the raw winner values the forward
+    saved (pool_raw_stats), read instead of gathering x at the argmax positions.  ``gm_dtype``: x's dtype by
+    default (every entry is a dout value or 0, so a bf16 gm holds what an f32 gm holds at half the bytes), f32 under
+    MIA_POOL_GM32=1, read at call time."""
     if win is not None and (win.dtype != x.dtype or win.numel() != n * (h // kh) * (w // kw) * c):
         raise ValueError("pool_bwd_gather: win must hold one x-typed value per pooled cell and channel")
+    if gm_dtype is None:
+        gm_dtype = torch.float32 if os.environ.get("MIA_POOL_GM32", "")[:1] == "1" else x.dtype
     dev = x.device
     g = torch.empty(2, c, dtype=torch.float32, device=dev)
-    gm = torch.empty(n * (h // kh) * (w // kw), c, dtype=torch.float32, device=dev)
+    gm = torch.empty(n * (h // kh) * (w // kw), c, dtype=gm_dtype, device=dev)
     lib = L.load()
     ws = workspace(lib.mia_bn_partial_bytes(n * h * w, c), dev, "bn")
-    L.check(lib.mia_pool_bwd_gather(dout.data_ptr(), out_layout, argmax.data_ptr(), x.data_ptr(), L.ptr(win),
-                                    L.dtype_code(x), n, h, w, c, kh, kw, bn.scale.data_ptr(), bn.shift.data_ptr(), bn.mean.data_ptr(),
-                                    bn.invstd.data_ptr(), gm.data_ptr(), g[0].data_ptr(), g[1].data_ptr(),
-                                    ws.data_ptr(), _s()), "mia_pool_bwd_gather")
+    L.check(lib.mia_pool_bwd_gather_ex(dout.data_ptr(), out_layout, argmax.data_ptr(), x.data_ptr(), L.ptr(win),
+                                       L.dtype_code(x), n, h, w, c, kh, kw, bn.scale.data_ptr(), bn.shift.data_ptr(),
+                                       bn.mean.data_ptr(), bn.invstd.data_ptr(), gm.data_ptr(), L.dtype_code(gm),
+                                       g[0].data_ptr(), g[1].data_ptr(), ws.data_ptr(), _s()),
+            "mia_pool_bwd_gather_ex")
     return gm, g[0], g[1]
 
 
 def pool_bn_relu_bwd_apply(gm, argmax, x, n, h, w, c, kh, kw, gamma, bn: BNState, dgamma, dbeta, dx, dbias=None):
-    """Dense half: BN backward of the pooled layer, g taken from gm at the argmax (one pass x -> dx)."""
+    """Dense half: BN backward of the pooled layer, g taken from gm (f32 or bf16) at the argmax (one pass x -> dx)."""
     lib = L.load()
     ws = workspace(lib.mia_bn_partial_bytes(n * h * w, c), x.device, "bn")
-    L.check(lib.mia_pool_bn_relu_bwd_apply(gm.data_ptr(), argmax.data_ptr(), x.data_ptr(), L.dtype_code(x), n, h, w,
-                                           c, kh, kw, L.ptr(gamma), bn.mean.data_ptr(), bn.invstd.data_ptr(),
-                                           dgamma.data_ptr(), dbeta.data_ptr(), dx.data_ptr(), L.ptr(dbias),
-                                           ws.data_ptr(), _s()), "mia_pool_bn_relu_bwd_apply")
+    L.check(lib.mia_pool_bn_relu_bwd_apply_ex(gm.data_ptr(), L.dtype_code(gm), argmax.data_ptr(), x.data_ptr(),
+                                              L.dtype_code(x), n, h, w, c, kh, kw, L.ptr(gamma), bn.mean.data_ptr(),
+                                              bn.invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                              dx.data_ptr(), L.ptr(dbias), ws.data_ptr(), _s()),
+            "mia_pool_bn_relu_bwd_apply_ex")
 
 
 def pool_fwd(x, n, h, w, c, kh, kw, bn: BNState, out, out_layout, argmax, win=None):

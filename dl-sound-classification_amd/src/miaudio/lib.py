@@ -102,6 +102,11 @@ SIGNATURES = {
                                       vp, vp, vp]),
     "mia_pool_bn_relu_bwd_apply": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp,
                                              vp, vp, vp]),
+    # include/miaudio_pool.h: the two above with gm in a dtype of the caller's choice
+    "mia_pool_bwd_gather_ex": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp,
+                                         i32, vp, vp, vp, vp]),
+    "mia_pool_bn_relu_bwd_apply_ex": (C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp,
+                                                vp, vp, vp, vp]),
     "mia_pool_fwd": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp]),
     "mia_pool_bwd_bn_relu_reduce": (C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp,
                                               vp, vp, vp, vp, vp, vp]),

@@ -274,7 +274,11 @@ int mia_pool_bwd_bn_relu_reduce(const void* dout, int32_t out_layout, const uint
 /* Pooled backward, sparse half: at the argmax position of every pooled cell,
  * gm[cell][c] = dout[cell][c] * (scale*x+shift > 0) (f32, NHWC cells (n, h/kh, w/kw, c)), and the BN
  * reductions dgamma = sum gm*xhat, dbeta = sum gm (the other kh*kw-1 window pixels carry no
- * gradient and are never read).  Replaces autograd of nn.MaxPool2d + nn.ReLU (envnet_v2.py:16-23). */
+ * gradient and are never read).  Replaces autograd of nn.MaxPool2d + nn.ReLU (envnet_v2.py:16-23).
+ * gm must be 16-byte aligned.  Every entry of gm is a dout value or 0: miaudio_pool.h has this pair of entry
+ * points with gm in the activation dtype (bf16 gm beside bf16 activations: the same results, half the bytes);
+ * the two below are those with an f32 gm.  MIA_POOL_V1=1 / MIA_POOL_GRID=n, read at call time, select the earlier
+ * kernels / cap the main kernel's grid (A/B runs and tests; the grid is part of the partial sums' rounding). */
 int mia_pool_bwd_gather(const void* dout, int32_t out_layout, const uint8_t* argmax, const void* x,
                         const void* win /* optional raw winners (n, h/kh, w/kw, c), x's dtype, or NULL */,
                         int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh, int32_t kw,
@@ -282,7 +286,7 @@ int mia_pool_bwd_gather(const void* dout, int32_t out_layout, const uint8_t* arg
                         float* gm, float* dgamma, float* dbeta, void* partial, mia_stream_t stream);
 /* Pooled backward, dense half (one read of x, one write of dx): BN backward
  * dx = gamma*invstd*(g - dbeta/P - xhat*dgamma/P), g = gm[cell] at the argmax position, else 0;
- * optional dbias[c] = sum_rows dx (nn.BatchNorm2d backward, envnet_v2.py:16,33). */
+ * optional dbias[c] = sum_rows dx (nn.BatchNorm2d backward, envnet_v2.py:16,33).  gm: 16-byte aligned. */
 int mia_pool_bn_relu_bwd_apply(const float* gm, const uint8_t* argmax, const void* x, int32_t dtype,
                                int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh, int32_t kw,
                                const float* gamma, const float* mean, const float* invstd,
