@@ -429,7 +429,6 @@ __device__ __forceinline__ void drop_keep4_queries(bool (&keep)[4], uint64_t key
   keep[3] = ((unsigned)(b >> 32) & 0xffffu) >= thr;
 }
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned fb_ld_flag(const unsigned* p) {
   unsigned v;

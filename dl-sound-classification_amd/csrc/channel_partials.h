@@ -20,7 +20,8 @@
 // on which block finishes first.  They do depend on nblk: the launch geometry is part of the result.
 //
 // The quantities: BN statistics q0 = sum (x - K), q1 = sum (x - K)^2; BN backward q0 = sum g (dbeta),
-// q1 = sum g xhat (dgamma); apply passes q0 = sum dx (the bias gradient of the layer below).
+// q1 = sum g xhat (dgamma); apply passes q0 = sum dx (the bias gradient of the layer below).  How g (the ReLU-masked
+// gradient), xhat and dx are formed per element, and with which roundings: bn_math.h.
 //
 // Producers of the layout that do not go through cp_fold, because their sums do not live in this thread map:
 //   fe_conv1 / fe_conv3 (feconv.hip), trunk_conv8 (conv8.hip): wave-persistent convolutions, one partial row per

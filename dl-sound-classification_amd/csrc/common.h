@@ -13,6 +13,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2_cvt __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // 16 B of raw words: eight bf16 as four (lo | hi << 16) pairs
 
 // two floats -> two bf16 (round to nearest even, as the (bf16) cast) packed lo | hi << 16: one v_cvt_pk_bf16_f32
 // (the two casts and the shift-or were four VALU instructions)
@@ -210,15 +211,29 @@ __device__ __forceinline__ float hash_u01(uint64_t seed, uint64_t idx) {
   return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
+// the two bf16 of a packed word (lo | hi << 16, pk_bf16's layout) as floats: exact, one VALU instruction each
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+// eight bf16 (16 B) -> f[2 i] = lo, f[2 i + 1] = hi of word i
+__device__ __forceinline__ void unpack8(u32x4 u, float (&f)[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = bf16_lo(u[i]);
+    f[2 * i + 1] = bf16_hi(u[i]);
+  }
+}
+__device__ __forceinline__ void unpack8(uint4 u, float (&f)[8]) { unpack8(u32x4{u.x, u.y, u.z, u.w}, f); }
+
 // 8 consecutive elements (16 B bf16 / 32 B f32, aligned) <-> 8 floats
 __device__ __forceinline__ void load8(const void* p, int dtype, int64_t off, float (&f)[8]) {
   if (dtype == MIA_BF16) {
+    // (unpack8 written out: one more level of inlining around f changes the code of every kernel that calls this)
     uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(p) + off);
     uint32_t w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __uint_as_float(w[i] << 16);
-      f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+      f[2 * i] = bf16_lo(w[i]);
+      f[2 * i + 1] = bf16_hi(w[i]);
     }
   } else {
     const float4* q = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + off);

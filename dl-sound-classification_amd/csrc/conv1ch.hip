@@ -37,6 +37,7 @@ struct C1Args {
   int n, oh, ow, h, wd, nchunk;
 };
 
+// the MIA_C1CH_V1 form (an oracle of the bit-identical forms tests: its text stays written out and off the shared headers)
 __global__ __launch_bounds__(256) void conv1ch_dgrad_kernel(C1Args g) {
   __shared__ __attribute__((aligned(16))) char rows[2][C1_SLOTS * C1_PSB];
   __shared__ __attribute__((aligned(16))) float outs[C1_HMAX * C1_OLD];

@@ -13,11 +13,11 @@
 // writes one f32 slab and a fixed-order reduce sums the slabs (bit-reproducible).
 #include <cstdlib>
 
+#include "bn_math.h"
 #include "channel_partials.h"
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
@@ -117,13 +117,13 @@ __global__ __launch_bounds__(256) void conv3_wgrad_kernel(W3Args g) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const uint32_t dw = R.d[s][k], yw = R.y[s][k];
-      float gv[2] = {__uint_as_float(dw << 16), __uint_as_float(dw & 0xffff0000u)};
-      const float xv[2] = {__uint_as_float(yw << 16), __uint_as_float(yw & 0xffff0000u)};
+      float gv[2] = {bf16_lo(dw), bf16_hi(dw)};
+      const float xv[2] = {bf16_lo(yw), bf16_hi(yw)};
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int i = 2 * k + j, c = (lane & 3) * 8 + i;
-        gv[j] = fmaf(xv[j], bnp[0][c], bnp[1][c]) > 0.f ? gv[j] : 0.f;
-        gv[j] = bnp[2][c] * (gv[j] - bnp[5][c] - (xv[j] - bnp[3][c]) * bnp[4][c] * bnp[6][c]);
+        gv[j] = bn_relu_on(xv[j], bnp[0][c], bnp[1][c]) ? gv[j] : 0.f;
+        gv[j] = bn_dx(gv[j], xv[j], bnp[2][c], bnp[3][c], bnp[4][c], bnp[5][c], bnp[6][c]);
         bs1[i] += gv[j];
       }
       o[k] = pk_bf16(gv[0], gv[1]);
@@ -223,6 +223,7 @@ __global__ __launch_bounds__(256) void conv3_wgrad_kernel(W3Args g) {
 // dw[e] = sum of the slabs (fixed order, bit-reproducible), e = co*64 + tap, in two coalesced stages:
 // stage 1: group g of C3_G sums its slabs in order into tmp[g][e] (double); stage 2: tmp summed in g order
 constexpr int C3_G = 64;
+// the MIA_REDUCE_V1 form (an oracle of the bit-identical forms tests: its text stays written out and off the shared headers)
 __global__ __launch_bounds__(256) void conv3_wgrad_reduce1_kernel(const float* __restrict__ part, int nslab,
                                                                   double* __restrict__ tmp) {
   const int e = blockIdx.x * 256 + threadIdx.x, gi = blockIdx.y;

@@ -18,12 +18,12 @@
 // and used for both pixel tiles: 160 ds_read_b128 per 256 MFMAs, ~80 B/clk per CU at the MFMA peak.
 // Each wave stages its own 71-pixel strip (row pitch 80 B: conflict-free b128 reads), so the waves
 // never wait for each other; the next row's raw loads fly while the current row computes.
+#include "bn_math.h"
 #include "channel_partials.h"
 
 #include <algorithm>
 #include <type_traits>
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -52,14 +52,7 @@ struct C8Args {
 __device__ __forceinline__ u32x4 cook(u32x4 u, bool ok, const float* sc, const float* sh) {
   if (!ok) return u32x4{0u, 0u, 0u, 0u};
   if (sc == nullptr) return u;
-  uint32_t w4[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float lo = fmaxf(fmaf(__uint_as_float(u[i] << 16), sc[2 * i], sh[2 * i]), 0.f);
-    const float hi = fmaxf(fmaf(__uint_as_float(u[i] & 0xffff0000u), sc[2 * i + 1], sh[2 * i + 1]), 0.f);
-    w4[i] = pk_bf16(lo, hi);
-  }
-  return u32x4{w4[0], w4[1], w4[2], w4[3]};
+  return bn_relu_pack(u, sc, sh);
 }
 
 #ifndef C8_EDGE
@@ -139,15 +132,14 @@ __global__ __launch_bounds__(C8_NT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
       }
     };
     auto store_row = [&]() __attribute__((always_inline)) {
-      float sc[8], sh[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { sc[i] = prm[cg * 8 + i]; sh[i] = prm[32 + cg * 8 + i]; }
+      BnFwd8 pre;
+      pre.load(cg, prm, prm + 32);
 #pragma unroll
       for (int s = 0; s < C8_LDC; ++s) {
         const int p = (lane + 64 * s) >> 2;
         if (p < C8_SPX)
           *reinterpret_cast<u32x4*>(strip + p * C8_PSB + cg * 16) =
-              cook(raw[s], (rok >> s) & 1u, PRE ? sc : nullptr, sh);
+              cook(raw[s], (rok >> s) & 1u, PRE ? pre.sc : nullptr, pre.sh);
       }
     };
     auto load_bx = [&](int oy) __attribute__((always_inline)) {
@@ -187,20 +179,19 @@ __global__ __launch_bounds__(C8_NT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
               const int e = 8 * h + 2 * i;
               w4[i] = pk_bf16(v[e] + bv[e], v[e + 1] + bv[e + 1]);
               if constexpr (STATS) {
-                const float d0 = __uint_as_float(w4[i] << 16) - bv[e], d1 = __uint_as_float(w4[i] & 0xffff0000u) - bv[e + 1];
+                const float d0 = bf16_lo(w4[i]) - bv[e], d1 = bf16_hi(w4[i]) - bv[e + 1];
                 s1[e] += d0; s2[e] = fmaf(d0, d0, s2[e]);
                 s1[e + 1] += d1; s2[e + 1] = fmaf(d1, d1, s2[e + 1]);
               }
               if constexpr (RED) {
                 const uint32_t xw = bxr[tt][h][i];
-                const float xv[2] = {__uint_as_float(xw << 16), __uint_as_float(xw & 0xffff0000u)};
-                const float dv[2] = {__uint_as_float(w4[i] << 16), __uint_as_float(w4[i] & 0xffff0000u)};
+                const float xv[2] = {bf16_lo(xw), bf16_hi(xw)};
+                const float dv[2] = {bf16_lo(w4[i]), bf16_hi(w4[i])};
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                   const int c = c0 + 16 * h + 2 * i + k;
-                  const float gk = fmaf(xv[k], prm[96 + c], prm[128 + c]) > 0.f ? dv[k] : 0.f;
-                  s1[e + k] += gk;
-                  s2[e + k] = fmaf(gk, (xv[k] - prm[160 + c]) * prm[192 + c], s2[e + k]);
+                  const float gk = bn_relu_on(xv[k], prm[96 + c], prm[128 + c]) ? dv[k] : 0.f;
+                  bn_red_step(gk, xv[k], prm[160 + c], prm[192 + c], s1[e + k], s2[e + k]);
                 }
               }
             }

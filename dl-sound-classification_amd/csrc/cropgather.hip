@@ -19,7 +19,6 @@
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void crop_gather_kernel(const uint32_t* __restrict__ store,
                                                           const int64_t* __restrict__ offsets, int64_t n_clips,

@@ -22,7 +22,7 @@
 // runs of 8 contiguous channels of one pixel and stores them as 16-B vectors without an LDS pass.
 // Measured at B=256 (tools/bench_fe.py): the load+store stream alone (no MFMA) takes 0.71 ms
 // (5.1 TB/s), the MFMA work alone 0.30-0.37 ms; the kernel lands at 0.98-1.15 ms.
-#include "common.h"
+#include "bn_math.h"
 
 #include <type_traits>
 
@@ -33,7 +33,6 @@ constexpr int FE_NT = 256;
 constexpr int FE_BM = 128;  // output pixels per item (4 waves: 2 channel halves x 2 pixel halves)
 constexpr int FE_N = 64;    // output channels
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <int CIN, int KW, int S>
 struct FeCfg {
@@ -70,17 +69,8 @@ __device__ __forceinline__ int fe_slot(int p) {
 __device__ __forceinline__ u32x4 fe_cook(u32x4 u, bool ok, bool pre, const float* sc, const float* sh) {
   if (!ok) return u32x4{0u, 0u, 0u, 0u};
   if (!pre) return u;
-  uint32_t w4[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float lo = fmaxf(fmaf(__uint_as_float(u[i] << 16), sc[2 * i], sh[2 * i]), 0.f);
-    const float hi = fmaxf(fmaf(__uint_as_float(u[i] & 0xffff0000u), sc[2 * i + 1], sh[2 * i + 1]), 0.f);
-    w4[i] = pk_bf16(lo, hi);
-  }
-  return u32x4{w4[0], w4[1], w4[2], w4[3]};
+  return bn_relu_pack(u, sc, sh);
 }
-
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) { return pk_bf16(lo, hi); }
 
 #ifdef FE_STAMP
 __device__ unsigned long long g_fe_st[64 * 4 * 256 * 8];
@@ -216,10 +206,10 @@ __global__ __launch_bounds__(FE_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         for (int h = 0; h < 2; ++h) {
           const int64_t e = (int64_t)m * FE_N + c0 + 16 * h;
           if (e < g.ylen) {
-            const u32x4 o = {pack2(v[8 * h] + bv[8 * h], v[8 * h + 1] + bv[8 * h + 1]),
-                             pack2(v[8 * h + 2] + bv[8 * h + 2], v[8 * h + 3] + bv[8 * h + 3]),
-                             pack2(v[8 * h + 4] + bv[8 * h + 4], v[8 * h + 5] + bv[8 * h + 5]),
-                             pack2(v[8 * h + 6] + bv[8 * h + 6], v[8 * h + 7] + bv[8 * h + 7])};
+            const u32x4 o = {pk_bf16(v[8 * h] + bv[8 * h], v[8 * h + 1] + bv[8 * h + 1]),
+                             pk_bf16(v[8 * h + 2] + bv[8 * h + 2], v[8 * h + 3] + bv[8 * h + 3]),
+                             pk_bf16(v[8 * h + 4] + bv[8 * h + 4], v[8 * h + 5] + bv[8 * h + 5]),
+                             pk_bf16(v[8 * h + 6] + bv[8 * h + 6], v[8 * h + 7] + bv[8 * h + 7])};
             *reinterpret_cast<u32x4*>(yb + e) = o;
           }
         }
@@ -390,8 +380,8 @@ __global__ __launch_bounds__(FS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             if (e < g.ylen) {
               const f32x4 u0 = *reinterpret_cast<const f32x4*>(sbias + c0 + 16 * h);
               const f32x4 u1 = *reinterpret_cast<const f32x4*>(sbias + c0 + 16 * h + 4);
-              const u32x4 o = {pack2(v[8 * h] + u0[0], v[8 * h + 1] + u0[1]), pack2(v[8 * h + 2] + u0[2], v[8 * h + 3] + u0[3]),
-                               pack2(v[8 * h + 4] + u1[0], v[8 * h + 5] + u1[1]), pack2(v[8 * h + 6] + u1[2], v[8 * h + 7] + u1[3])};
+              const u32x4 o = {pk_bf16(v[8 * h] + u0[0], v[8 * h + 1] + u0[1]), pk_bf16(v[8 * h + 2] + u0[2], v[8 * h + 3] + u0[3]),
+                               pk_bf16(v[8 * h + 4] + u1[0], v[8 * h + 5] + u1[1]), pk_bf16(v[8 * h + 6] + u1[2], v[8 * h + 7] + u1[3])};
               *reinterpret_cast<u32x4*>(yb + e) = o;
             }
           }
@@ -582,7 +572,7 @@ __global__ __launch_bounds__(256) void fe_conv1_kernel(F1Args g) {
         w4[i] = pk_bf16(v[e] + bv[e], v[e + 1] + bv[e + 1]);
         if constexpr (STATS) {
           if (op < g.w1) {
-            const float d0 = __uint_as_float(w4[i] << 16) - bv[e], d1 = __uint_as_float(w4[i] & 0xffff0000u) - bv[e + 1];
+            const float d0 = bf16_lo(w4[i]) - bv[e], d1 = bf16_hi(w4[i]) - bv[e + 1];
             s1[e] += d0; s2[e] = fmaf(d0, d0, s2[e]);
             s1[e + 1] += d1; s2[e + 1] = fmaf(d1, d1, s2[e + 1]);
           }
@@ -754,7 +744,7 @@ __global__ __launch_bounds__(256) void fe_conv3_kernel(F3Args g) {
         w4[i] = pk_bf16(v[e] + bv[e], v[e + 1] + bv[e + 1]);
         if constexpr (STATS) {
           if (ox < g.ow) {
-            const float d0 = __uint_as_float(w4[i] << 16) - bv[e], d1 = __uint_as_float(w4[i] & 0xffff0000u) - bv[e + 1];
+            const float d0 = bf16_lo(w4[i]) - bv[e], d1 = bf16_hi(w4[i]) - bv[e + 1];
             s1[e] += d0; s2[e] = fmaf(d0, d0, s2[e]);
             s1[e + 1] += d1; s2[e + 1] = fmaf(d1, d1, s2[e + 1]);
           }
@@ -915,16 +905,7 @@ __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
       if (q < WCH) {
         u32x4 v = w[s];
         if constexpr (PRE) {
-          if (2 * o0 + p < g.win) {
-            uint32_t w4[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const float lo = fmaxf(fmaf(__uint_as_float(v[i] << 16), sc[2 * i], sh[2 * i]), 0.f);
-              const float hi = fmaxf(fmaf(__uint_as_float(v[i] & 0xffff0000u), sc[2 * i + 1], sh[2 * i + 1]), 0.f);
-              w4[i] = pk_bf16(lo, hi);
-            }
-            v = u32x4{w4[0], w4[1], w4[2], w4[3]};
-          }
+          if (2 * o0 + p < g.win) v = bn_relu_pack(v, sc, sh);
         }
         const int slot = (p & 1) * HALF + (p >> 1);
         *reinterpret_cast<u32x4*>(win + slot * PSB + cgw * 16) = v;
@@ -1053,6 +1034,7 @@ int fe_grid1(int items) {  // one workgroup per CU
 }
 
 // dw[e] = sum over slabs (fixed order: deterministic)
+// the MIA_REDUCE_V1 form (an oracle of the bit-identical forms tests: its text stays written out and off the shared headers)
 __global__ __launch_bounds__(256) void fw_reduce_kernel(const float* __restrict__ ws, int slabs, int len,
                                                         float* __restrict__ out) {
   const int e = blockIdx.x * 256 + threadIdx.x;

@@ -101,8 +101,8 @@ static __device__ __forceinline__ void ld16(const void* p, int dtype, int64_t id
       const uint32_t w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        f[8 * h + 2 * i] = __uint_as_float(w[i] << 16);
-        f[8 * h + 2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        f[8 * h + 2 * i] = bf16_lo(w[i]);
+        f[8 * h + 2 * i + 1] = bf16_hi(w[i]);
       }
     }
   } else {

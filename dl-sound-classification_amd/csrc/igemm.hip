@@ -81,12 +81,7 @@ __device__ __forceinline__ void load_chunk(const OpDev& o, int64_t off, int nval
           return;
         }
       }
-      uint32_t w4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(w4[i] << 16);
-        f[2 * i + 1] = __uint_as_float(w4[i] & 0xffff0000u);
-      }
+      unpack8(u, f);
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) f[i] = i < nvalid ? (float)p[i] : 0.f;

@@ -12,6 +12,7 @@
 // Every reduction runs in a fixed order (no atomics): results are bit-identical run to run.
 #include <algorithm>
 
+#include "bn_math.h"
 #include "channel_partials.h"
 #include "pcen_math.h"
 
@@ -74,10 +75,7 @@ __global__ __launch_bounds__(NT) void lt_pool_stats_kernel(const void* __restric
       }
       if (w < OT) {
         const int64_t aoff = ((int64_t)b * OT + w) * C + cg * 8;
-        uint32_t a0 = 0, a1 = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { a0 |= (uint32_t)arg[i] << (8 * i); a1 |= (uint32_t)arg[i + 4] << (8 * i); }
-        *reinterpret_cast<uint2*>(argmax + aoff) = make_uint2(a0, a1);
+        *reinterpret_cast<uint2*>(argmax + aoff) = argmax_pack(arg);
         store8(win, dtype, aoff, bestraw);  // exact: z's own dtype
       }
     }
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(NT) void lt_pool_apply_kernel(const void* __restric
     float f[8], v[8];
     load8(win, dtype, e * 8, f);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = fmaxf(fmaf(f[i], scale[cg * 8 + i], shift[cg * 8 + i]), 0.f);
+    for (int i = 0; i < 8; ++i) v[i] = bn_relu(f[i], scale[cg * 8 + i], shift[cg * 8 + i]);
     store8(out, odt, e * 8, v);
   }
 }
@@ -110,14 +108,14 @@ __global__ __launch_bounds__(NT) void lt_pool_apply_mean_kernel(const void* __re
   const int e = blockIdx.x * NT + threadIdx.x;
   if (e >= n * G) return;
   const int b = e / G, cg = e - b * G;
-  float sc[8], sh[8], acc[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { sc[i] = scale[cg * 8 + i]; sh[i] = shift[cg * 8 + i]; acc[i] = 0.f; }
+  BnFwd8 bn;
+  bn.load(cg, scale, shift);
+  float acc[8] = {0};
   for (int j = 0; j < OT; ++j) {
     float f[8];
     load8(win, dtype, ((int64_t)b * OT + j) * C + cg * 8, f);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] += fmaxf(fmaf(f[i], sc[i], sh[i]), 0.f);
+    for (int i = 0; i < 8; ++i) acc[i] += bn_relu(f[i], bn.sc[i], bn.sh[i]);
   }
   const float inv = 1.f / (float)OT;
 #pragma unroll
@@ -141,11 +139,8 @@ __global__ __launch_bounds__(NT) void lt_pool_bwd_gather_kernel(const void* __re
 #pragma unroll
   for (int i = 0; i < 8; ++i) { s1[i] = 0.f; s2[i] = 0.f; }
   if (rs < rslots) {
-    float sc[8], sh[8], mu[8], is[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      sc[i] = scale[cg * 8 + i]; sh[i] = shift[cg * 8 + i]; mu[i] = mean[cg * 8 + i]; is[i] = invstd[cg * 8 + i];
-    }
+    BnRed8 bn;
+    bn.load(cg, scale, shift, mean, invstd);
     const float inv = 1.f / (float)OT;
     const int cells = n * OT;  // < 2^31 (checked by the launcher)
     for (int u = blockIdx.x * rslots + rs; u < cells; u += gridDim.x * rslots) {
@@ -160,11 +155,7 @@ __global__ __launch_bounds__(NT) void lt_pool_bwd_gather_kernel(const void* __re
         load8(dout, ddt, off, d);
       }
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        g[i] = fmaf(f[i], sc[i], sh[i]) > 0.f ? d[i] : 0.f;
-        s1[i] += g[i];
-        s2[i] = fmaf(g[i], (f[i] - mu[i]) * is[i], s2[i]);
-      }
+      for (int i = 0; i < 8; ++i) g[i] = bn.step(i, d[i], f[i], s1[i], s2[i]);
       store8(gm, MIA_F32, off, g);
     }
   }
@@ -189,16 +180,8 @@ __global__ __launch_bounds__(NT) void lt_pool_bwd_apply_kernel(const float* __re
 #pragma unroll
   for (int i = 0; i < 8; ++i) { s1[i] = 0.f; s2[i] = 0.f; }
   if (rs < rslots) {
-    float mu[8], is[8], a[8], mb[8], mg[8];
-    const float invP = 1.f / (float)((int64_t)n * T);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int c = cg * 8 + i;
-      mu[i] = mean[c]; is[i] = invstd[c];
-      a[i] = (gamma ? gamma[c] : 1.f) * is[i];
-      mb[i] = dbeta[c] * invP;
-      mg[i] = dgamma[c] * invP;
-    }
+    BnApply8 bn;
+    bn.load(cg, gamma, mean, invstd, dgamma, dbeta, 1.f / (float)((int64_t)n * T));
     const int units = n * NW;
     for (int u = blockIdx.x * rslots + rs; u < units; u += gridDim.x * rslots) {
       const int b = u / NW, w = u - b * NW;
@@ -218,10 +201,8 @@ __global__ __launch_bounds__(NT) void lt_pool_bwd_apply_kernel(const float* __re
         load8(z, dtype, base + (int64_t)j * C, x);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          const uint32_t word = i < 4 ? am.x : am.y;
-          const int av = (int)((word >> (8 * (i & 3))) & 0xffu);
-          const float gi = (av == j && w < OT) ? gv[i] : 0.f;
-          g[i] = a[i] * (gi - mb[i] - (x[i] - mu[i]) * is[i] * mg[i]);
+          const float gi = (argmax_byte(am, i) == j && w < OT) ? gv[i] : 0.f;
+          g[i] = bn.dx(i, gi, x[i]);
           s1[i] += g[i];
         }
         store8(dz, dtype, base + (int64_t)j * C, g);

@@ -140,6 +140,7 @@ __device__ __forceinline__ float soft_ce_row(const float* __restrict__ zr, const
 }
 
 // One block; wave w handles rows w, w+16, ...  (the MIA_REDUCE_V1 form, and the form for B > CE_MAXB)
+// (an oracle of the bit-identical forms tests: its text stays written out and off the shared headers)
 constexpr int CE_NT = 1024;
 __global__ __launch_bounds__(CE_NT) void soft_ce_kernel(const float* __restrict__ logits, const float* __restrict__ y,
                                                         int B, int C, int input_sigmoid, float* loss_out,

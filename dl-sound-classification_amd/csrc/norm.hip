@@ -7,6 +7,7 @@
 // The BN *apply* never takes its own pass in the forward: the consumer GEMM applies
 // scale/shift (+ReLU) while staging its operand (MIA_PRE_AFFINE_RELU), and the pool kernel does
 // the same for the pooled layers.
+#include "bn_math.h"
 #include "channel_partials.h"
 
 namespace {
@@ -84,11 +85,8 @@ __global__ __launch_bounds__(NT) void bn_relu_bwd_reduce_kernel(const void* __re
                                                                 float* __restrict__ partial) {
   const int t = threadIdx.x;
   const int G = C / 8, cg = t % G, rs = t / G, rslots = NT / G;
-  float sc[8], sh[8], mu[8], is[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sc[i] = scale[cg * 8 + i]; sh[i] = shift[cg * 8 + i]; mu[i] = mean[cg * 8 + i]; is[i] = invstd[cg * 8 + i];
-  }
+  BnRed8 bn;
+  bn.load(cg, scale, shift, mean, invstd);
   float s1[8] = {0}, s2[8] = {0};
   for (int64_t r = (int64_t)blockIdx.x * rslots + rs; r < P; r += (int64_t)gridDim.x * rslots) {
     float g[8], xv[8];
@@ -96,12 +94,7 @@ __global__ __launch_bounds__(NT) void bn_relu_bwd_reduce_kernel(const void* __re
     load8(dact, dtype, off, g);
     load8(x, dtype, off, xv);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float z = fmaf(xv[i], sc[i], sh[i]);
-      g[i] = z > 0.f ? g[i] : 0.f;
-      s1[i] += g[i];
-      s2[i] = fmaf(g[i], (xv[i] - mu[i]) * is[i], s2[i]);
-    }
+    for (int i = 0; i < 8; ++i) g[i] = bn.step(i, g[i], xv[i], s1[i], s2[i]);
     if (dz) store8(dz, dtype, off, g);
   }
   cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);
@@ -122,22 +115,11 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const void* __restrict
                                                           const float* __restrict__ shift = nullptr) {
   const int t = threadIdx.x;
   const int G = C / 8, cg = t % G, rs = t / G, rslots = NT / G;
-  float a[8], mu[8], is[8], mb[8], mg[8], sc[8], sh[8];
-  if constexpr (MASK) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { sc[i] = scale[cg * 8 + i]; sh[i] = shift[cg * 8 + i]; }
-  }
+  BnFwd8 m;
+  if constexpr (MASK) m.load(cg, scale, shift);
   float s1[8] = {0}, s2[8] = {0};
-  const float invP = 1.f / (float)P;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int c = cg * 8 + i;
-    is[i] = invstd[c];
-    a[i] = (gamma ? gamma[c] : 1.f) * is[i];
-    mu[i] = mean[c];
-    mb[i] = dbeta[c] * invP;
-    mg[i] = dgamma[c] * invP;
-  }
+  BnApply8 bn;
+  bn.load(cg, gamma, mean, invstd, dgamma, dbeta, 1.f / (float)P);
   for (int64_t r = (int64_t)blockIdx.x * rslots + rs; r < P; r += (int64_t)gridDim.x * rslots) {
     float g[8], xv[8];
     const int64_t off = r * C + cg * 8;
@@ -145,8 +127,8 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const void* __restrict
     load8(x, dtype, off, xv);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      if constexpr (MASK) g[i] = fmaf(xv[i], sc[i], sh[i]) > 0.f ? g[i] : 0.f;
-      g[i] = a[i] * (g[i] - mb[i] - (xv[i] - mu[i]) * is[i] * mg[i]);
+      if constexpr (MASK) g[i] = bn_relu_on(xv[i], m.sc[i], m.sh[i]) ? g[i] : 0.f;
+      g[i] = bn.dx(i, g[i], xv[i]);
       s1[i] += g[i];
     }
     store8(dx, dtype, off, g);

@@ -26,7 +26,6 @@
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WG = 256;
 

@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include "../../include/miaudio_pool.h"
+#include "bn_math.h"
 #include "channel_partials.h"
 
 namespace {
@@ -65,7 +66,7 @@ __device__ __forceinline__ void pool_window_dt(const void* __restrict__ x, int d
     for (int pos = 0; pos < KH * KW; ++pos)
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const float v = fmaxf(fmaf(f[pos][i], sc[i], sh[i]), 0.f);
+        const float v = bn_relu(f[pos][i], sc[i], sh[i]);
         if (v > best[i]) { best[i] = v; raw[i] = f[pos][i]; arg[i] = pos; }
       }
   } else {
@@ -76,7 +77,7 @@ __device__ __forceinline__ void pool_window_dt(const void* __restrict__ x, int d
         const int pos = dy * kw + dx;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          const float v = fmaxf(fmaf(f[i], sc[i], sh[i]), 0.f);
+          const float v = bn_relu(f[i], sc[i], sh[i]);
           if (v > best[i]) { best[i] = v; raw[i] = f[i]; arg[i] = pos; }
         }
       }
@@ -111,20 +112,14 @@ __global__ __launch_bounds__(NT) void pool_fwd_kernel(const void* __restrict__ x
     p /= OW;
     const int oy = p % OH;
     const int b = p / OH;
-    float sc[8], sh[8], best[8], raw[8];
+    BnFwd8 bn;
+    float best[8], raw[8];
     int arg[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      sc[i] = scale ? scale[cg * 8 + i] : 1.f;
-      sh[i] = shift ? shift[cg * 8 + i] : 0.f;
-    }
-    pool_window<KH, KW>(x, dtype, (((int64_t)b * H + oy * kh) * W + ox * kw) * C + cg * 8, W, C, kh, kw, sc, sh, best,
-                        raw, arg);
+    bn.load_or_identity(cg, scale, shift);
+    pool_window<KH, KW>(x, dtype, (((int64_t)b * H + oy * kh) * W + ox * kw) * C + cg * 8, W, C, kh, kw, bn.sc, bn.sh,
+                        best, raw, arg);
     const int64_t aoff = (((int64_t)b * OH + oy) * OW + ox) * C + cg * 8;
-    uint32_t a0 = 0, a1 = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { a0 |= (uint32_t)arg[i] << (8 * i); a1 |= (uint32_t)arg[i + 4] << (8 * i); }
-    *reinterpret_cast<uint2*>(argmax + aoff) = make_uint2(a0, a1);
+    *reinterpret_cast<uint2*>(argmax + aoff) = argmax_pack(arg);
     if (win) store8(win, dtype, aoff, raw);  // the winner's raw x (exact: x's own dtype) for the backward
     if (layout == 0) {
       store8(out, dtype, aoff, best);  // NHWC: the 8 channels are one 16-B (bf16) / 32-B (f32) run
@@ -165,20 +160,14 @@ __global__ __launch_bounds__(NT) void pool_fwd_tr_kernel(const void* __restrict_
     const int cg = chunk * (PT / 8) + ch;
     if (r >= np || cg >= G) continue;
     const int p = p0 + r, oy = p / OW, ox = p - oy * OW;
-    float sc[8], sh[8], best[8], raw[8];
+    BnFwd8 bn;
+    float best[8], raw[8];
     int arg[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      sc[i] = scale ? scale[cg * 8 + i] : 1.f;
-      sh[i] = shift ? shift[cg * 8 + i] : 0.f;
-    }
-    pool_window<KH, KW>(x, dtype, (((int64_t)b * H + oy * kh) * W + ox * kw) * C + cg * 8, W, C, kh, kw, sc, sh, best,
-                        raw, arg);
+    bn.load_or_identity(cg, scale, shift);
+    pool_window<KH, KW>(x, dtype, (((int64_t)b * H + oy * kh) * W + ox * kw) * C + cg * 8, W, C, kh, kw, bn.sc, bn.sh,
+                        best, raw, arg);
     const int64_t aoff = ((int64_t)b * S + p) * C + cg * 8;
-    uint32_t a0 = 0, a1 = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { a0 |= (uint32_t)arg[i] << (8 * i); a1 |= (uint32_t)arg[i + 4] << (8 * i); }
-    *reinterpret_cast<uint2*>(argmax + aoff) = make_uint2(a0, a1);
+    *reinterpret_cast<uint2*>(argmax + aoff) = argmax_pack(arg);
     if (win) store8(win, dtype, aoff, raw);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -257,11 +246,8 @@ __global__ __launch_bounds__(NT) void pool_raw_stats_kernel(const bf16* __restri
       const bf16* row = x + (((int64_t)b * H + iy) * W + (int64_t)ox * kw) * C + cg * 8;
 #pragma unroll 4
       for (int dx = 0; dx < kw; ++dx) {
-        const uint4 u = *reinterpret_cast<const uint4*>(row + (int64_t)dx * C);
-        const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
         float f[8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w4[i] << 16); f[2 * i + 1] = __uint_as_float(w4[i] & 0xffff0000u); }
+        unpack8(*reinterpret_cast<const uint4*>(row + (int64_t)dx * C), f);
         const int pos = dy * kw + dx;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -274,16 +260,8 @@ __global__ __launch_bounds__(NT) void pool_raw_stats_kernel(const bf16* __restri
       }
     }
     const int64_t aoff = (((int64_t)b * OH + oy) * OW + ox) * C + cg * 8;
-    uint32_t a0 = 0, a1 = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { a0 |= (uint32_t)arg[i] << (8 * i); a1 |= (uint32_t)arg[i + 4] << (8 * i); }
-    *reinterpret_cast<uint2*>(argmax + aoff) = make_uint2(a0, a1);
-    uint32_t o4[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      o4[i] = pk_bf16(bestraw[2 * i], bestraw[2 * i + 1]);  // exact: bf16 inputs
-    }
-    *reinterpret_cast<uint4*>(win + aoff) = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+    *reinterpret_cast<uint2*>(argmax + aoff) = argmax_pack(arg);
+    store8(win, MIA_BF16, aoff, bestraw);  // exact: bf16 inputs
   }
   // pixels right of the last full window (W % kw of them per row) enter the statistics only
   const int tailw = W - OW * kw;
@@ -292,13 +270,13 @@ __global__ __launch_bounds__(NT) void pool_raw_stats_kernel(const bf16* __restri
     int p = idx / G;
     const int tx = p % tailw;
     const int r = p / tailw;  // b * H + iy
-    const uint4 u = *reinterpret_cast<const uint4*>(x + ((int64_t)r * W + OW * kw + tx) * C + cg * 8);
-    const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
+    float f[8];
+    unpack8(*reinterpret_cast<const uint4*>(x + ((int64_t)r * W + OW * kw + tx) * C + cg * 8), f);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float lo = __uint_as_float(w4[i] << 16) - ks[2 * i], hi = __uint_as_float(w4[i] & 0xffff0000u) - ks[2 * i + 1];
-      s1[2 * i] += lo; s2[2 * i] = fmaf(lo, lo, s2[2 * i]);
-      s1[2 * i + 1] += hi; s2[2 * i + 1] = fmaf(hi, hi, s2[2 * i + 1]);
+    for (int i = 0; i < 8; ++i) {
+      const float d = f[i] - ks[i];
+      s1[i] += d;
+      s2[i] = fmaf(d, d, s2[i]);
     }
   }
   // block reduction of the shifted sums per channel (threads with equal cg), fixed order
@@ -325,7 +303,7 @@ __global__ __launch_bounds__(NT) void pool_apply_kernel(const bf16* __restrict__
     const int ox = (int)(p % OW);
     p /= OW;
     const int oy = (int)(p % OH), b = (int)(p / OH);
-    const float v = fmaxf(fmaf((float)win[e], scale[c], shift[c]), 0.f);
+    const float v = bn_relu((float)win[e], scale[c], shift[c]);
     st_elem(out, dtype, out_index(layout, b, oy, ox, c, OH, OW, C), v);
   }
 }
@@ -349,7 +327,7 @@ __global__ __launch_bounds__(256) void pool_apply_t64_kernel(const bf16* __restr
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int c = ch * 8 + i;
-      tile[c][r] = (bf16)fmaxf(fmaf((float)v[i], scale[c], shift[c]), 0.f);
+      tile[c][r] = (bf16)bn_relu((float)v[i], scale[c], shift[c]);
     }
   }
   __syncthreads();
@@ -380,11 +358,8 @@ __global__ __launch_bounds__(NT) void pool_bwd_kernel(const void* __restrict__ d
   const int OH = H / kh, OW = W / kw, G = C / 8;
   const int t = threadIdx.x;
   const int cg = t % G, rs = t / G, rslots = NT / G;
-  float sc[8], sh[8], mu[8], is[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sc[i] = scale[cg * 8 + i]; sh[i] = shift[cg * 8 + i]; mu[i] = mean[cg * 8 + i]; is[i] = invstd[cg * 8 + i];
-  }
+  BnRed8 bn;
+  bn.load(cg, scale, shift, mean, invstd);
   float s1[8] = {0}, s2[8] = {0};
   const int P = n * H * W;  // < 2^31 (checked by the launcher): 32-bit index math
   for (int r = blockIdx.x * rslots + rs; r < P; r += gridDim.x * rslots) {
@@ -403,22 +378,16 @@ __global__ __launch_bounds__(NT) void pool_bwd_kernel(const void* __restrict__ d
       const uint2 am = *reinterpret_cast<const uint2*>(argmax + aoff);
       float xv[8];
       if (dtype == MIA_BF16) {
-        uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(x) + off);
-        uint32_t w4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { xv[2 * i] = __uint_as_float(w4[i] << 16); xv[2 * i + 1] = __uint_as_float(w4[i] & 0xffff0000u); }
+        unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16*>(x) + off), xv);
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) xv[i] = reinterpret_cast<const float*>(x)[off + i];
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const uint32_t word = i < 4 ? am.x : am.y;
-        const int a = (int)((word >> (8 * (i & 3))) & 0xffu);
-        if (a == pos && fmaf(xv[i], sc[i], sh[i]) > 0.f) {
+        if (argmax_byte(am, i) == pos && bn_relu_on(xv[i], bn.sc[i], bn.sh[i])) {
           g[i] = ld_elem(dout, dtype, out_index(layout, b, oy, ox, cg * 8 + i, OH, OW, C));
-          s1[i] += g[i];
-          s2[i] = fmaf(g[i], (xv[i] - mu[i]) * is[i], s2[i]);
+          bn_red_step(g[i], xv[i], bn.mu[i], bn.is[i], s1[i], s2[i]);
         }
       }
     }
@@ -435,6 +404,7 @@ __global__ __launch_bounds__(NT) void pool_bwd_kernel(const void* __restrict__ d
 // win (optional, NHWC cells, x's dtype): the raw winner value of each cell saved by the forward
 // (pool_raw_stats); when given, x is not gathered at all -- a contiguous read replaces kh*kw-strided
 // 2-byte gathers that each touch a separate cache line.
+// (the MIA_POOL_V1 oracle of the forms tests: its text stays written out, off bn_math.h and the shared fold)
 __global__ __launch_bounds__(NT) void pool_bwd_sparse_kernel(const void* __restrict__ dout, int layout,
                                                              const uint8_t* __restrict__ argmax,
                                                              const void* __restrict__ x,
@@ -514,9 +484,7 @@ struct Raw8 {
   }
   __device__ __forceinline__ void unpack(float (&f)[8]) const {
     if constexpr (DT == MIA_BF16) {
-      const uint32_t w[4] = {v[0].x, v[0].y, v[0].z, v[0].w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
+      unpack8(v[0], f);
     } else {
       const uint32_t w[8] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w};
 #pragma unroll
@@ -548,11 +516,8 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_ra_kernel(const void* __re
   const int G = C / 8;
   const int t = threadIdx.x;
   const int cg = t % G, rs = t / G, rslots = NT / G;
-  float sc[8], sh[8], mu[8], is[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sc[i] = scale[cg * 8 + i]; sh[i] = shift[cg * 8 + i]; mu[i] = mean[cg * 8 + i]; is[i] = invstd[cg * 8 + i];
-  }
+  BnRed8 bn;
+  bn.load(cg, scale, shift, mean, invstd);
   float s1[8] = {0}, s2[8] = {0};
   const int stride = gridDim.x * rslots;  // cells + D * stride < 2^31 (checked by the launcher)
   for (int cell0 = blockIdx.x * rslots + rs; cell0 < cells; cell0 += D * stride) {
@@ -574,10 +539,10 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_ra_kernel(const void* __re
       dr[v].unpack(dv);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const float g = fmaf(xv[i], sc[i], sh[i]) > 0.f ? dv[i] : 0.f;
-        gv[i] = g;
-        s1[i] = live ? s1[i] + g : s1[i];
-        s2[i] = live ? fmaf(g, (xv[i] - mu[i]) * is[i], s2[i]) : s2[i];
+        float t1 = s1[i], t2 = s2[i];
+        gv[i] = bn.step(i, dv[i], xv[i], t1, t2);
+        s1[i] = live ? t1 : s1[i];
+        s2[i] = live ? t2 : s2[i];
       }
       if (live) store8(gm, GDT, (int64_t)(cell0 + v * stride) * C + cg * 8, gv);
     }
@@ -611,11 +576,8 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_tr_kernel(const void* __re
   const int LD = C + 4;  // tile row (one cell) in floats: 16-B aligned rows
   __shared__ __attribute__((aligned(16))) float red[NT * 16];  // the dout tile [rslots][LD] until the final combine
   float* tile = red;
-  float sc[8], sh[8], mu[8], is[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sc[i] = scale[cg * 8 + i]; sh[i] = shift[cg * 8 + i]; mu[i] = mean[cg * 8 + i]; is[i] = invstd[cg * 8 + i];
-  }
+  BnRed8 bn;
+  bn.load(cg, scale, shift, mean, invstd);
   float s1[8] = {0}, s2[8] = {0};
   const int es = dtype == MIA_BF16 ? 1 : 2;
   const uintptr_t dbase = reinterpret_cast<uintptr_t>(dout) >> es;  // dout's address in elements
@@ -633,8 +595,8 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_tr_kernel(const void* __re
       if (c0 + 3 < cells && b0 == b3 && ((dbase + (uintptr_t)i0) & 3) == 0) {
         if (dtype == MIA_BF16) {
           const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16*>(dout) + i0);
-          pv[u][0] = __uint_as_float(v.x << 16); pv[u][1] = __uint_as_float(v.x & 0xffff0000u);
-          pv[u][2] = __uint_as_float(v.y << 16); pv[u][3] = __uint_as_float(v.y & 0xffff0000u);
+          pv[u][0] = bf16_lo(v.x); pv[u][1] = bf16_hi(v.x);
+          pv[u][2] = bf16_lo(v.y); pv[u][3] = bf16_hi(v.y);
         } else {
           const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(dout) + i0);
           pv[u][0] = v.x; pv[u][1] = v.y; pv[u][2] = v.z; pv[u][3] = v.w;
@@ -672,20 +634,14 @@ __global__ __launch_bounds__(NT) void pool_bwd_sparse_tr_kernel(const void* __re
         const uint2 am = *reinterpret_cast<const uint2*>(argmax + cell * C + cg * 8);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          const uint32_t word = i < 4 ? am.x : am.y;
-          const int a = (int)((word >> (8 * (i & 3))) & 0xffu);
+          const int a = argmax_byte(am, i);
           const int iy = oy * kh + a / kw, ix = ox * kw + a % kw;
           xv[i] = ld_elem(x, dtype, (((int64_t)b * H + iy) * W + ix) * C + cg * 8 + i);
         }
       }
       float gv[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float g = fmaf(xv[i], sc[i], sh[i]) > 0.f ? dv[i] : 0.f;
-        gv[i] = g;
-        s1[i] += g;
-        s2[i] = fmaf(g, (xv[i] - mu[i]) * is[i], s2[i]);
-      }
+      for (int i = 0; i < 8; ++i) gv[i] = bn.step(i, dv[i], xv[i], s1[i], s2[i]);
       store8(gm, gdt, cell * C + cg * 8, gv);
     }
     __syncthreads();  // also the barrier between the last tile reads and the fold's writes to red
@@ -717,16 +673,8 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_oct_kernel(const void* _
   const int t = threadIdx.x;
   const int cg = t % G;
   const int P = n * H * W;
-  float mu[8], is[8], a[8], mb[8], mg[8];
-  const float invP = 1.f / (float)P;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int c = cg * 8 + i;
-    mu[i] = mean[c]; is[i] = invstd[c];
-    a[i] = (gamma ? gamma[c] : 1.f) * is[i];
-    mb[i] = dbeta[c] * invP;
-    mg[i] = dgamma[c] * invP;
-  }
+  BnApply8 bn;
+  bn.load(cg, gamma, mean, invstd, dgamma, dbeta, 1.f / (float)P);
   float s1[8] = {0};
   const int64_t units = (int64_t)n * H * NO * G;
   for (int64_t u = (int64_t)blockIdx.x * NT + t; u < units; u += (int64_t)gridDim.x * NT) {
@@ -763,11 +711,9 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_oct_kernel(const void* _
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int i = 2 * q + h;
-          const float xv = __uint_as_float(h ? (w4[q] & 0xffff0000u) : (w4[q] << 16));
-          const uint32_t word = i < 4 ? am.x : am.y;
-          const int av = (int)((word >> (8 * (i & 3))) & 0xffu);
-          const float gi = cell && av == pos0 + j ? gv[i] : 0.f;
-          g[h] = a[i] * (gi - mb[i] - (xv - mu[i]) * is[i] * mg[i]);
+          const float xv = h ? bf16_hi(w4[q]) : bf16_lo(w4[q]);
+          const float gi = cell && argmax_byte(am, i) == pos0 + j ? gv[i] : 0.f;
+          g[h] = bn.dx(i, gi, xv);
           s1[i] += g[h];
         }
         o4[q] = pk_bf16(g[0], g[1]);
@@ -800,16 +746,8 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const void* _
   const int t = threadIdx.x;
   const int cg = t % G;
   const int P = n * H * W;
-  float mu[8], is[8], a[8], mb[8], mg[8];
-  const float invP = 1.f / (float)P;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int c = cg * 8 + i;
-    mu[i] = mean[c]; is[i] = invstd[c];
-    a[i] = (gamma ? gamma[c] : 1.f) * is[i];
-    mb[i] = dbeta[c] * invP;
-    mg[i] = dgamma[c] * invP;
-  }
+  BnApply8 bn;
+  bn.load(cg, gamma, mean, invstd, dgamma, dbeta, 1.f / (float)P);
   float s1[8] = {0};
   const int units = n * H * NR * G;  // < 2^31 (checked by the launcher)
   const int stride = gridDim.x * NT;
@@ -857,11 +795,9 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const void* _
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const int i = 2 * q + h;
-            const float xv = __uint_as_float(h ? (w4[q] & 0xffff0000u) : (w4[q] << 16));
-            const uint32_t word = i < 4 ? am[v].x : am[v].y;
-            const int av = (int)((word >> (8 * (i & 3))) & 0xffu);
-            const float gi = av == pos0[v] + j ? gv[i] : 0.f;
-            g[h] = a[i] * (gi - mb[i] - (xv - mu[i]) * is[i] * mg[i]);
+            const float xv = h ? bf16_hi(w4[q]) : bf16_lo(w4[q]);
+            const float gi = argmax_byte(am[v], i) == pos0[v] + j ? gv[i] : 0.f;
+            g[h] = bn.dx(i, gi, xv);
             s1[i] += g[h];
           }
           o4[q] = pk_bf16(g[0], g[1]);
@@ -882,6 +818,8 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const void* _
 #ifndef PB_RUNS
 #define PB_RUNS 1  // runs per thread-iteration: 1, 2, 3 measured equal within 5% (block 0: 0.34-0.36 ms)
 #endif
+// the per-pixel form (MIA_POOL_BWD_PIXEL, and every f32 / long-window layer): the oracle of the run and octet forms
+// in tests/test_gpu_pool_forms.py, so its prologue and apply expression stay written out, off bn_math.h
 template <int GDT>
 __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_kernel(const void* __restrict__ gm,
                                                                const uint8_t* __restrict__ argmax,
@@ -1141,6 +1079,15 @@ static int pool_bn_bwd_apply_launch(const void* gm, const uint8_t* argmax, const
   const int rslots = NT / (c / 8);
   const int64_t P = (int64_t)n * h * w;
   const int64_t units = (int64_t)n * h * ((w + 7) / 8) * (c / 8);
+  // every form ends the same way: its launch check, then the final pass of the dx sums (dbias) over its nb rows
+  auto finish = [&](const char* what, int nb) -> int {
+    MIA_LAUNCH_CHECK(what);
+    if (dbias) {
+      cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
+      MIA_LAUNCH_CHECK("pool_bn_bwd_apply_final");
+    }
+    return 0;
+  };
   if (kw % 8 == 0 && dtype == MIA_BF16 && units < (1ll << 31) &&
       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(units, NT), CP_MAXBLK));
@@ -1148,12 +1095,7 @@ static int pool_bn_bwd_apply_launch(const void* gm, const uint8_t* argmax, const
                                                         make_fastdiv((w + 7) / 8), make_fastdiv(h), make_fastdiv(c / 8),
                                                         gamma, mean, invstd, dgamma, dbeta, reinterpret_cast<bf16*>(dx),
                                                         dbias ? (float*)partial : nullptr);
-    MIA_LAUNCH_CHECK("pool_bn_bwd_apply");
-    if (dbias) {
-      cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
-      MIA_LAUNCH_CHECK("pool_bn_bwd_apply_final");
-    }
-    return 0;
+    return finish("pool_bn_bwd_apply", nb);
   }
   const int64_t runs = (int64_t)n * h * cdiv(w, kw) * (c / 8);
   static const bool per_pixel = getenv("MIA_POOL_BWD_PIXEL") != nullptr;  // A/B switch: the per-pixel form
@@ -1174,23 +1116,13 @@ static int pool_bn_bwd_apply_launch(const void* gm, const uint8_t* argmax, const
     else
       pool_bn_bwd_apply_run_kernel<4, RU, GDT><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma,
                                                                  mean, invstd, dgamma, dbeta, dxb, part);
-    MIA_LAUNCH_CHECK("pool_bn_bwd_apply_run");
-    if (dbias) {
-      cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
-      MIA_LAUNCH_CHECK("pool_bn_bwd_apply_final");
-    }
-    return 0;
+    return finish("pool_bn_bwd_apply_run", nb);
   }
   const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(P, (int64_t)rslots * 8), CP_MAXBLK));
   pool_bn_bwd_apply_kernel<GDT><<<nb, NT, 0, s>>>(gm, argmax, x, dtype, n, h, w, c, kh, kw, make_fastdiv(w),
                                                   make_fastdiv(h), make_fastdiv(kw), make_fastdiv(kh), gamma, mean,
                                                   invstd, dgamma, dbeta, dx, dbias ? (float*)partial : nullptr);
-  MIA_LAUNCH_CHECK("pool_bn_bwd_apply");
-  if (dbias) {
-    cp_final2_kernel<<<(unsigned)c, 256, 0, s>>>((const float*)partial, nb, c, /*q0 = sum dx*/ dbias, nullptr);
-    MIA_LAUNCH_CHECK("pool_bn_bwd_apply_final");
-  }
-  return 0;
+  return finish("pool_bn_bwd_apply", nb);
 }
 
 extern "C" int mia_pool_bn_relu_bwd_apply_ex(const void* gm, int32_t gm_dtype, const uint8_t* argmax, const void* x,

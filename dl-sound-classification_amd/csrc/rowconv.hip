@@ -1,6 +1,7 @@
 // Row-window direct convolution (mia_gemm path 1) and its weight gradient (path 2) for the EnvNet-v2
 // trunk / frontend conv shapes, bf16 MFMA, gfx950: the input row segment a block reads is staged once in
 // LDS and every im2col element is an LDS read of that window (section comments below).
+#include "bn_math.h"
 #include "gemm_common.h"
 
 namespace {
@@ -20,7 +21,6 @@ constexpr int NT = 256;
 // The weight tile (N x 128 of the packed [N][KH][KW][C] matrix) is double-buffered; the window
 // is single-buffered and swapped only when ky advances.  MFMA 32x32x16 bf16, 4 waves, each
 // owning BM/4 output pixels x all N channels.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Loads are issued unconditionally (out-of-range chunks read the tensor base instead) and kept raw in
 // registers; zero padding, the producer's BN affine + ReLU and the bf16 pack are applied when the
@@ -43,8 +43,7 @@ __device__ __forceinline__ u32x4 cook_raw(const RawChunk& r, bool ok, const floa
   if constexpr (sizeof(TS) == 2 && !PRE) return r.a;
   float f[8];
   if constexpr (sizeof(TS) == 2) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(r.a[i] << 16); f[2 * i + 1] = __uint_as_float(r.a[i] & 0xffff0000u); }
+    unpack8(r.a, f);
   } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) { f[i] = __uint_as_float(r.a[i]); f[4 + i] = __uint_as_float(r.b[i]); }
@@ -111,11 +110,8 @@ __global__ __launch_bounds__(NT) void rowconv_kernel(RowArgs g) {
   const int px0 = x0 * S - g.pw;            // input column of window pixel 0
   const int cg = t % Cfg::CG;               // this thread's channel chunk (constant: CG | NT)
 
-  float sc[8], sh[8];
-  if constexpr (PRE) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { sc[i] = g.ps[cg * 8 + i]; sh[i] = g.pt[cg * 8 + i]; }
-  }
+  BnFwd8 pre;
+  if constexpr (PRE) pre.load(cg, g.ps, g.pt);
 
   RawChunk wraw[Cfg::WCH];
   uint32_t wok = 0;
@@ -145,7 +141,7 @@ __global__ __launch_bounds__(NT) void rowconv_kernel(RowArgs g) {
       const int p = q / Cfg::CG;
       if (p < Cfg::WPX)
         *reinterpret_cast<u32x4*>(win + win_slot<S, Cfg::HALF>(p) * Cfg::PSB + cg * 16) =
-            cook_raw<TS, PRE>(wraw[s], (wok >> s) & 1u, sc, sh, relu);
+            cook_raw<TS, PRE>(wraw[s], (wok >> s) & 1u, pre.sc, pre.sh, relu);
     }
   };
   auto load_b = [&](int kt) __attribute__((always_inline)) {
@@ -290,11 +286,8 @@ __global__ __launch_bounds__(NT) void rowwgrad_kernel(RowWArgs g) {
   const int64_t nchunks = (int64_t)g.n * g.oh * CPR;
   const int cg = t % CG;
 
-  float sc[8], sh[8];
-  if constexpr (PRE) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { sc[i] = g.ps[cg * 8 + i]; sh[i] = g.pt[cg * 8 + i]; }
-  }
+  BnFwd8 pre;
+  if constexpr (PRE) pre.load(cg, g.ps, g.pt);
 
   RawChunk wraw[KYB][WCH];
   RawChunk draw[DCH];
@@ -339,7 +332,7 @@ __global__ __launch_bounds__(NT) void rowwgrad_kernel(RowWArgs g) {
     for (int s = 0; s < DCH; ++s) {
       const int q = t + NT * s;
       const int p = q / (NOUT / 8), cc = q % (NOUT / 8);
-      *reinterpret_cast<u32x4*>(dyt + p * DSB + cc * 16) = cook_raw<T, false>(draw[s], (dok >> s) & 1u, sc, sh, false);
+      *reinterpret_cast<u32x4*>(dyt + p * DSB + cc * 16) = cook_raw<T, false>(draw[s], (dok >> s) & 1u, pre.sc, pre.sh, false);
     }
 #pragma unroll
     for (int kyi = 0; kyi < KYB; ++kyi)
@@ -349,7 +342,7 @@ __global__ __launch_bounds__(NT) void rowwgrad_kernel(RowWArgs g) {
       const int p = q / CG;
       if (p < WPX)
         *reinterpret_cast<u32x4*>(win + kyi * WBYTES + win_slot<S, HALF>(p) * PSB + cg * 16) =
-            cook_raw<T, PRE>(wraw[kyi][s], (wok >> (kyi * WCH + s)) & 1u, sc, sh, relu);
+            cook_raw<T, PRE>(wraw[kyi][s], (wok >> (kyi * WCH + s)) & 1u, pre.sc, pre.sh, relu);
     }
   };
 

@@ -4,6 +4,7 @@
 // (mia_fe_conv1_wgrad_bn, which instantiates the same weight-gradient kernel).  Section comments below.
 #include <cstdlib>
 
+#include "bn_math.h"
 #include "gemm_common.h"
 
 namespace {
@@ -11,7 +12,6 @@ namespace {
 using namespace mgemm;
 
 constexpr int NT = 256;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // -------------------------------------------------------------------------- single-channel tap wgrad
 // dW[n][ky][kx] = sum_{b,oy,ox} dY[b,oy,ox,n] * X[b, oy+ky, S*ox+kx]  for the 1-channel convs of
@@ -41,6 +41,7 @@ struct TapWArgs {
 };
 
 template <typename TD, typename TX, int S, int KH, int KW, bool BNB = false>
+// (BNB: the MIA_CONV1W_V1 oracle of conv1_wgrad_bn_kernel, its BN arithmetic written out, off bn_math.h)
 __global__ __launch_bounds__(NT) void tapwgrad_kernel(TapWArgs g) {
   constexpr int BP = 256;
   constexpr int NS = KW / S;                       // taps per parity sequence
@@ -417,18 +418,17 @@ __global__ __launch_bounds__(NT, 2) void conv1_wgrad_bn_kernel(TapWArgs g) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           float gv[2], yv[2];
-          gv[0] = __uint_as_float(R.d[s2][i] << 16);
-          gv[1] = __uint_as_float(R.d[s2][i] & 0xffff0000u);
-          yv[0] = __uint_as_float(R.y[s2][i] << 16);
-          yv[1] = __uint_as_float(R.y[s2][i] & 0xffff0000u);
+          gv[0] = bf16_lo(R.d[s2][i]);
+          gv[1] = bf16_hi(R.d[s2][i]);
+          yv[0] = bf16_lo(R.y[s2][i]);
+          yv[1] = bf16_hi(R.y[s2][i]);
           uint32_t m = 0;
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const int ch = 2 * i + h;
-            const bool on = fmaf(yv[h], bsc[ch], bsh[ch]) > 0.f;
+            const bool on = bn_relu_on(yv[h], bsc[ch], bsh[ch]);
             const float d = on ? gv[h] : 0.f;
-            sdz[ch] += d;
-            sdx[ch] = fmaf(d, (yv[h] - bmu[ch]) * bis[ch], sdx[ch]);
+            bn_red_step(d, yv[h], bmu[ch], bis[ch], sdz[ch], sdx[ch]);
             sy[ch] += yv[h];
             m |= on ? (0xffffu << (16 * h)) : 0u;
           }

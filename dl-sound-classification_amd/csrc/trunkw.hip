@@ -15,13 +15,10 @@
 // Ashift (one pass over dY) and the BN+ReLU'd input a = bf16(relu(x*scale + shift)) (one pass over
 // x) -- the same rounding as the pre-op the implicit GEMM applies while staging -- and the GEMM
 // runs on the dense LDS-DMA kernel at MFMA rate instead of the gathered implicit GEMM.
-#include "common.h"
+#include "bn_math.h"
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t pk(float lo, float hi) { return pk_bf16(lo, hi); }
 
 // out = bf16(relu(x * scale + shift)), 8 channels per thread
 __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const bf16* __restrict__ x, int64_t P, int C,
@@ -31,15 +28,7 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const bf16* __restri
   const int64_t total = P * G;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c0 = (int)(i % G) * 8;
-    const u32x4 v = reinterpret_cast<const u32x4*>(x)[i];
-    u32x4 o;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float lo = fmaxf(fmaf(__uint_as_float(v[q] << 16), sc[c0 + 2 * q], sh[c0 + 2 * q]), 0.f);
-      const float hi = fmaxf(fmaf(__uint_as_float(v[q] & 0xffff0000u), sc[c0 + 2 * q + 1], sh[c0 + 2 * q + 1]), 0.f);
-      o[q] = pk(lo, hi);
-    }
-    reinterpret_cast<u32x4*>(out)[i] = o;
+    reinterpret_cast<u32x4*>(out)[i] = bn_relu_pack(reinterpret_cast<const u32x4*>(x)[i], sc + c0, sh + c0);
   }
 }
 

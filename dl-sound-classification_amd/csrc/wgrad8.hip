@@ -12,6 +12,7 @@
 // split-K reducer sums the slabs.  Operands are transposed LDS reads (ds_read_b64_tr_b16) of the
 // [px][32 ch] images, exactly as the row-window wgrad kernel.  Rows for step s+1 are loaded raw
 // into registers while step s computes (issue early, convert + write late).
+#include "bn_math.h"
 #include "gemm_common.h"
 
 namespace mgemm {
@@ -39,25 +40,12 @@ constexpr int W8_DROW = W8_BP * 64;         // bytes per staged dY row
 constexpr int W8_XCH = (W8_WPX * 4 + W8_NT - 1) / W8_NT;  // 16-B chunks per thread per input row (2)
 
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ bf16x8 tr_frag(const char* p0, int stride) {
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MIA_LDS s16x4*)(p0));
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MIA_LDS s16x4*)(p0 + 4 * stride));
   const s16x8 c = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8, c);
-}
-
-__device__ __forceinline__ u32x4 bn_relu_pack(u32x4 u, bool ok, const float* sc, const float* sh) {
-  if (!ok) return u32x4{0u, 0u, 0u, 0u};
-  uint32_t w4[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float lo = fmaxf(fmaf(__uint_as_float(u[i] << 16), sc[2 * i], sh[2 * i]), 0.f);
-    const float hi = fmaxf(fmaf(__uint_as_float(u[i] & 0xffff0000u), sc[2 * i + 1], sh[2 * i + 1]), 0.f);
-    w4[i] = pk_bf16(lo, hi);
-  }
-  return u32x4{w4[0], w4[1], w4[2], w4[3]};
 }
 
 __global__ __launch_bounds__(W8_NT) void wgrad8_kernel(W8Args g) {
@@ -68,9 +56,8 @@ __global__ __launch_bounds__(W8_NT) void wgrad8_kernel(W8Args g) {
   const int ky = __builtin_amdgcn_readfirstlane(t >> 6);
   const int i16 = lane & 15, gq = lane >> 4;
   const int cg = t & 3;  // this thread's 8-channel group in every staged 16-B chunk
-  float sc[8], sh[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { sc[i] = g.ps[cg * 8 + i]; sh[i] = g.pt[cg * 8 + i]; }
+  BnFwd8 bn;
+  bn.load(cg, g.ps, g.pt);
 
   f32x16 acc[8];
 #pragma unroll
@@ -113,7 +100,7 @@ __global__ __launch_bounds__(W8_NT) void wgrad8_kernel(W8Args g) {
       for (int i = 0; i < W8_XCH; ++i) {
         const int q = t + W8_NT * i;
         if ((q >> 2) < W8_WPX)
-          *reinterpret_cast<u32x4*>(ring + slot * W8_XROW + q * 16) = bn_relu_pack(xr[i], (xok >> i) & 1u, sc, sh);
+          *reinterpret_cast<u32x4*>(ring + slot * W8_XROW + q * 16) = (xok >> i) & 1u ? bn_relu_pack(xr[i], bn.sc, bn.sh) : u32x4{0u, 0u, 0u, 0u};
       }
     };
     auto store_dy = [&](int buf) __attribute__((always_inline)) {
