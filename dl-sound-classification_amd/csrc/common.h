@@ -49,6 +49,27 @@ static inline hipStream_t as_stream(mia_stream_t s) { return reinterpret_cast<hi
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// n / d for 0 <= n < 2^31 without an integer division (Granlund-Montgomery: one mul_hi, add, shift)
+struct FastDiv {
+  uint32_t d, m, l;
+};
+static inline FastDiv make_fastdiv(uint32_t d) {
+  uint32_t l = 0;
+  while ((1u << l) < d) ++l;
+  const uint32_t m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - d)) / d + 1);
+  return FastDiv{d, m, l};
+}
+__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) { return (__umulhi(n, f.m) + n) >> f.l; }
+
+// Row map of an elementwise producer's output (miaudio_rowmap.h): pixel x of source row r (w pixels a row) is stored
+// at pixel lead + r * rowpx + x; the lead pixels before row 0 and pixels w .. rowpx - 1 of every row are written as
+// zeros, and so are the zc16 16-B pieces at zp (optional).  {0, w, nullptr, 0} is the dense layout.
+struct RowMap {
+  int lead, rowpx;
+  void* zp;
+  int zc16;
+};
+
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }

@@ -220,6 +220,214 @@ __global__ __launch_bounds__(256) void conv3_wgrad_kernel(W3Args g) {
   }
 }
 
+// conv3_wgrad_kernel<true> rescheduled (the default of mia_conv3_wgrad_bn; MIA_C3W_V1=1 selects the kernel above, the
+// oracle of tests/test_gpu_conv3w_forms.py, whose text stays written out).  Same items per wave (it = gw + k * nw),
+// same four MFMAs per item in the same order, same bn_chunk expressions and bs1 add order: every slab, every dyo
+// byte and every bpart row is the same bits.  What differs is the schedule:
+//   - (seg, oy, b) is decoded once per wave and carried from item to item by the precomputed step of nw items
+//     (scalar adds and compares, no division in the loop); the loads and the dyo store share it;
+//   - two items of loads are in flight while one computes (a ring of three register sets, the loop unrolled by
+//     three so that the sets never move);
+//   - BNREG: the lane's 7 x 8 BN constants (its eight channels are fixed) live in registers instead of being read
+//     from LDS per element.
+struct W3Step { int dseg, doy, db; };  // nw items further: seg += dseg, oy += doy, b += db (with carries)
+struct W3Pos { int seg, oy, b; };
+
+template <bool BNREG>
+__global__ __launch_bounds__(256) void conv3_wgrad_bn2_kernel(W3Args g, W3Step st) {
+  constexpr int ROWB = 80, CPYB = 704;
+  __shared__ __attribute__((aligned(16))) char strip[4][4 * CPYB];
+  __shared__ __attribute__((aligned(16))) char dyt[4][32 * 64];
+  __shared__ __attribute__((aligned(16))) float bnp[7][32];
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int gw = blockIdx.x * 4 + wv, nw = gridDim.x * 4;
+  const int items = g.n * g.oh * g.nseg;
+  char* sg = strip[wv];
+  char* dt = dyt[wv];
+  f32x16 acc[2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { acc[0][i] = 0.f; acc[1][i] = 0.f; }
+  struct Raw { u32x2 v[3]; u32x4 d[2]; u32x4 y[2]; uint32_t ok; };
+  float bs1[8];
+  if (threadIdx.x < 32) {
+    const int c = threadIdx.x;
+    const float invP = 1.f / (float)g.P;
+    const float is = g.invstd[c];
+    bnp[0][c] = g.scale[c];
+    bnp[1][c] = g.shift[c];
+    bnp[2][c] = (g.gamma ? g.gamma[c] : 1.f) * is;
+    bnp[3][c] = g.mean[c];
+    bnp[4][c] = is;
+    bnp[5][c] = g.dbeta[c] * invP;
+    bnp[6][c] = g.dgamma[c] * invP;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) bs1[i] = 0.f;
+  __syncthreads();
+  float creg[BNREG ? 7 : 1][8];
+  if constexpr (BNREG) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) creg[k][i] = bnp[k][(lane & 3) * 8 + i];
+  }
+  auto cst = [&](int k, int i) __attribute__((always_inline)) -> float {
+    if constexpr (BNREG) return creg[k][i];
+    else return bnp[k][(lane & 3) * 8 + i];
+  };
+  // item idx follows the item at p by nw; past the end the position stays (its loads are issued, never used)
+  auto next = [&](const W3Pos& p, int idx) __attribute__((always_inline)) -> W3Pos {
+    if (idx >= items) return p;
+    W3Pos q = p;
+    q.seg += st.dseg;
+    const int c0 = q.seg >= g.nseg ? 1 : 0;
+    q.seg -= c0 ? g.nseg : 0;
+    q.oy += st.doy + c0;
+    const int c1 = q.oy >= g.oh ? 1 : 0;
+    q.oy -= c1 ? g.oh : 0;
+    q.b += st.db + c1;
+    return q;
+  };
+  auto load = [&](const W3Pos& p) __attribute__((always_inline)) {
+    Raw R;
+    const int l = lane < 40 ? lane : lane - 40;  // lanes 40..63 load lanes 0..23's bytes (not staged)
+    const int r = l / 5, q = l % 5;
+    const int col = p.seg * 32 + 8 * q;
+    const bf16* src = g.x + ((int64_t)p.b * g.h + p.oy + r) * g.wd;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int c = col + 4 * k;
+      R.v[k] = c + 4 <= g.wd ? *reinterpret_cast<const u32x2*>(src + c) : u32x2{0u, 0u};
+    }
+    const int64_t drow = ((int64_t)p.b * g.oh + p.oy) * g.ow * 32;
+    R.ok = 0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int qq = lane + 64 * s;
+      const int px = p.seg * 32 + (qq >> 2);
+      const int64_t off = drow + (int64_t)px * 32 + (qq & 3) * 8;
+      R.d[s] = px < g.ow ? *reinterpret_cast<const u32x4*>(g.dy + off) : u32x4{0u, 0u, 0u, 0u};
+      R.y[s] = px < g.ow ? *reinterpret_cast<const u32x4*>(g.ya + off) : u32x4{0u, 0u, 0u, 0u};
+      R.ok |= (uint32_t)(px < g.ow) << s;
+    }
+    return R;
+  };
+  const int i16 = lane & 15, gq = lane >> 4, h = lane >> 5;
+  const int n = lane & 31;  // tap within an N tile: ky = 4*nt + (n >> 3), kx = n & 7
+  auto bn_chunk = [&](const Raw& R, int s, const W3Pos& p) __attribute__((always_inline)) -> u32x4 {
+    if (!((R.ok >> s) & 1u)) return u32x4{0u, 0u, 0u, 0u};
+    uint32_t o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t dw = R.d[s][k], yw = R.y[s][k];
+      float gv[2] = {bf16_lo(dw), bf16_hi(dw)};
+      const float xv[2] = {bf16_lo(yw), bf16_hi(yw)};
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int i = 2 * k + j;
+        gv[j] = bn_relu_on(xv[j], cst(0, i), cst(1, i)) ? gv[j] : 0.f;
+        gv[j] = bn_dx(gv[j], xv[j], cst(2, i), cst(3, i), cst(4, i), cst(5, i), cst(6, i));
+        bs1[i] += gv[j];
+      }
+      o[k] = pk_bf16(gv[0], gv[1]);
+    }
+    const int qq = lane + 64 * s;
+    const int px = p.seg * 32 + (qq >> 2);
+    const u32x4 v = {o[0], o[1], o[2], o[3]};
+    *reinterpret_cast<u32x4*>(g.dyo + (((int64_t)p.b * g.oh + p.oy) * g.ow + px) * 32 + (qq & 3) * 8) = v;
+    return v;
+  };
+  auto run = [&](const Raw& R, const W3Pos& p) __attribute__((always_inline)) {
+    u32x4 dv[2];
+    dv[0] = bn_chunk(R, 0, p);
+    dv[1] = bn_chunk(R, 1, p);
+    wave_sync();  // the previous item's fragment reads are done (common.h)
+    if (lane < 40) {
+      const int l = lane;
+      const int r = l / 5, q = l % 5;
+      const uint32_t d[6] = {R.v[0][0], R.v[0][1], R.v[1][0], R.v[1][1], R.v[2][0], R.v[2][1]};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        uint32_t o[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int e = c + 2 * i;
+          o[i] = (e & 1) ? ((d[e >> 1] >> 16) | (d[(e >> 1) + 1] << 16)) : d[e >> 1];
+        }
+        *reinterpret_cast<u32x4*>(sg + c * CPYB + r * ROWB + 16 * q) = u32x4{o[0], o[1], o[2], o[3]};
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int qq = lane + 64 * s;
+      *reinterpret_cast<u32x4*>(dt + (qq >> 2) * 64 + (qq & 3) * 16) = dv[s];
+    }
+    wave_sync();
+    const int kx = n & 7, cp = kx & 3;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int kr = ks * 16 + 8 * (gq >> 1) + (i16 >> 2);
+      const int c4 = 16 * (gq & 1) + 4 * (i16 & 3);
+      const bf16x8 fa = tr_frag(dt + kr * 64 + c4 * 2, 64);
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const int ky = 4 * nt + (n >> 3);
+        const char* src = sg + cp * CPYB + ky * ROWB + 2 * (16 * ks + 8 * h + (kx & 4));
+        const u32x2 p0 = *reinterpret_cast<const u32x2*>(src);
+        const u32x2 p1 = *reinterpret_cast<const u32x2*>(src + 8);
+        const u32x4 f = {p0[0], p0[1], p1[0], p1[1]};
+        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, f), acc[nt], 0, 0, 0);
+      }
+    }
+  };
+
+  int it = gw;
+  if (it < items) {
+    W3Pos p0;
+    {
+      const int rest = it / g.nseg;  // the one decode of this wave
+      p0.seg = it - rest * g.nseg;
+      p0.b = rest / g.oh;
+      p0.oy = rest - p0.b * g.oh;
+    }
+    W3Pos p1 = next(p0, it + nw), p2 = next(p1, it + 2 * nw);
+    Raw r0 = load(p0), r1 = load(p1), r2;
+    for (;;) {
+      r2 = load(p2);
+      run(r0, p0);
+      it += nw;
+      if (it >= items) break;
+      p0 = next(p2, it + 2 * nw);
+      r0 = load(p0);
+      run(r1, p1);
+      it += nw;
+      if (it >= items) break;
+      p1 = next(p0, it + 2 * nw);
+      r1 = load(p1);
+      run(r2, p2);
+      it += nw;
+      if (it >= items) break;
+      p2 = next(p1, it + 2 * nw);
+    }
+  }
+  float* dst = g.part + (int64_t)gw * 2048;
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int co = (r & 3) + 8 * (r >> 2) + 4 * h;
+      dst[co * 64 + nt * 32 + n] = acc[nt][r];
+    }
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int m = 4; m < 64; m <<= 1) bs1[i] += __shfl_xor(bs1[i], m, 64);
+  if (lane < 4) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) g.bpart[(int64_t)gw * 32 + lane * 8 + i] = bs1[i];
+  }
+}
+
 // dw[e] = sum of the slabs (fixed order, bit-reproducible), e = co*64 + tap, in two coalesced stages:
 // stage 1: group g of C3_G sums its slabs in order into tmp[g][e] (double); stage 2: tmp summed in g order
 constexpr int C3_G = 64;
@@ -312,7 +520,23 @@ extern "C" int mia_conv3_wgrad_bn(const void* x, const void* da, const void* ya,
   double* tmp = reinterpret_cast<double*>(part + (int64_t)nwaves * 2048);
   a.bpart = reinterpret_cast<float*>(tmp + (int64_t)C3_G * 2048);
   hipStream_t s = as_stream(stream);
-  conv3_wgrad_kernel<true><<<nwaves / 4, 256, 0, s>>>(a);
+  // A/B switches, read at call time: MIA_C3W_V1=1 the kernel before the reschedule, MIA_C3W_BNLDS=1 the rescheduled
+  // kernel with its BN constants read from LDS; MIA_C3W_GRID=n at most n blocks, whichever kernel runs (it only
+  // lowers the grid: the tests use it to make a wave walk many items at small shapes)
+  const char* e = getenv("MIA_C3W_GRID");
+  const int cap = e ? atoi(e) : 0;
+  const int nblk = cap > 0 ? std::min(nwaves / 4, cap) : nwaves / 4;
+  nwaves = nblk * 4;
+  const char* v1 = getenv("MIA_C3W_V1");
+  const char* lds = getenv("MIA_C3W_BNLDS");
+  if (v1 && v1[0] == '1') {
+    conv3_wgrad_kernel<true><<<nblk, 256, 0, s>>>(a);
+  } else {
+    const int t = nwaves / a.nseg;
+    const W3Step st{nwaves % a.nseg, t % a.oh, t / a.oh};
+    if (lds && lds[0] == '1') conv3_wgrad_bn2_kernel<false><<<nblk, 256, 0, s>>>(a, st);
+    else conv3_wgrad_bn2_kernel<true><<<nblk, 256, 0, s>>>(a, st);
+  }
   MIA_LAUNCH_CHECK("conv3_wgrad_bn");
   conv3_wgrad_reduce1(part, nwaves, tmp, s);
   conv3_wgrad_reduce2_kernel<<<8, 256, 0, s>>>(tmp, dw);

@@ -7,6 +7,7 @@
 // The BN *apply* never takes its own pass in the forward: the consumer GEMM applies
 // scale/shift (+ReLU) while staging its operand (MIA_PRE_AFFINE_RELU), and the pool kernel does
 // the same for the pooled layers.
+#include "../../include/miaudio_rowmap.h"
 #include "bn_math.h"
 #include "channel_partials.h"
 
@@ -102,7 +103,9 @@ __global__ __launch_bounds__(NT) void bn_relu_bwd_reduce_kernel(const void* __re
 
 // MASK: dz is the gradient of relu(bn(x)) and the ReLU mask is recomputed from x (scale/shift),
 // so the reduce pass never has to write the masked gradient out.
-template <bool MASK>
+// RM: dx through a row map (RowMap, common.h; P < 2^31): the thread that owns a row's last pixel also zeroes that
+// row's pixels w .. rowpx - 1, the one that owns pixel 0 the lead pixels, block 0 the zero pixel.
+template <bool MASK, bool RM = false>
 __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const void* __restrict__ dz, const void* __restrict__ x,
                                                           void* dx, int dtype, int64_t P, int C,
                                                           const float* __restrict__ gamma,
@@ -112,7 +115,8 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const void* __restrict
                                                           const float* __restrict__ dbeta,
                                                           float* __restrict__ partial,
                                                           const float* __restrict__ scale = nullptr,
-                                                          const float* __restrict__ shift = nullptr) {
+                                                          const float* __restrict__ shift = nullptr,
+                                                          RowMap rm = RowMap{}, int w = 0, FastDiv dW = FastDiv{}) {
   const int t = threadIdx.x;
   const int G = C / 8, cg = t % G, rs = t / G, rslots = NT / G;
   BnFwd8 m;
@@ -120,6 +124,10 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const void* __restrict
   float s1[8] = {0}, s2[8] = {0};
   BnApply8 bn;
   bn.load(cg, gamma, mean, invstd, dgamma, dbeta, 1.f / (float)P);
+  if constexpr (RM) {
+    if (rm.zp && blockIdx.x == 0)
+      for (int i = t; i < rm.zc16; i += NT) reinterpret_cast<uint4*>(rm.zp)[i] = uint4{0u, 0u, 0u, 0u};
+  }
   for (int64_t r = (int64_t)blockIdx.x * rslots + rs; r < P; r += (int64_t)gridDim.x * rslots) {
     float g[8], xv[8];
     const int64_t off = r * C + cg * 8;
@@ -131,7 +139,18 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const void* __restrict
       g[i] = bn.dx(i, g[i], xv[i]);
       s1[i] += g[i];
     }
-    store8(dx, dtype, off, g);
+    if constexpr (RM) {
+      const int row = (int)fdiv((uint32_t)r, dW), ix = (int)r - row * w;
+      const int64_t pix = rm.lead + (int64_t)row * rm.rowpx + ix;
+      store8(dx, dtype, pix * C + cg * 8, g);
+      const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (ix == w - 1)
+        for (int px = 1; px <= rm.rowpx - w; ++px) store8(dx, dtype, (pix + px) * C + cg * 8, z);
+      if (r == 0)
+        for (int px = 0; px < rm.lead; ++px) store8(dx, dtype, (int64_t)px * C + cg * 8, z);
+    } else {
+      store8(dx, dtype, off, g);
+    }
   }
   if (partial) cp_fold<2>(s1, s2, C, G, rslots, blockIdx.x, partial);  // slot 1: zeros
 }
@@ -596,23 +615,44 @@ extern "C" int mia_bn_bwd_apply(const void* dz, const void* x, void* dx, int32_t
   return 0;
 }
 
-extern "C" int mia_bn_relu_bwd_apply(const void* dact, const void* x, void* dx, int32_t dtype, int64_t P, int32_t C,
-                                     const float* gamma, const float* scale, const float* shift, const float* mean,
-                                     const float* invstd, const float* dgamma, const float* dbeta, float* dbias,
-                                     void* partial, mia_stream_t stream) {
+extern "C" int mia_bn_relu_bwd_apply_rows(const void* dact, const void* x, void* dx, int32_t dtype, int64_t P,
+                                          int32_t C, int32_t w, int32_t lead, int32_t row_pixels, void* zero_pixel,
+                                          int32_t zc, const float* gamma, const float* scale, const float* shift,
+                                          const float* mean, const float* invstd, const float* dgamma,
+                                          const float* dbeta, float* dbias, void* partial, mia_stream_t stream) {
   if (int r = check_bn(x, dtype, P, C)) return r;
   MIA_CHECK_ARG(dact && dx && scale && shift && mean && invstd && dgamma && dbeta, "bn_relu_bwd_apply: null pointer");
   MIA_CHECK_ARG(!dbias || partial, "bn_relu_bwd_apply: dbias needs the partial workspace");
+  MIA_CHECK_ARG(w > 0 && P % w == 0 && lead >= 0 && row_pixels >= w && zc >= 0 && zc % 8 == 0 && (zc == 0 || zero_pixel),
+                "bn_relu_bwd_apply: bad row map (w %d, lead %d, row_pixels %d, zc %d)", w, lead, row_pixels, zc);
   const int nb = nblocks_for(P, C);
   hipStream_t s = as_stream(stream);
-  bn_bwd_apply_kernel<true><<<nb, NT, 0, s>>>(dact, x, dx, dtype, P, C, gamma, mean, invstd, dgamma, dbeta,
-                                              dbias ? (float*)partial : nullptr, scale, shift);
+  if (lead != 0 || row_pixels != w || zc) {
+    MIA_CHECK_ARG(P < (1ll << 31) && dx != dact, "bn_relu_bwd_apply: a row map needs P < 2^31 and dx apart from dact");
+    MIA_CHECK_ARG(aligned16(dx) && (!zc || aligned16(zero_pixel)), "bn_relu_bwd_apply: dx / zero_pixel alignment");
+    const int es = dtype == MIA_BF16 ? 2 : 4;
+    const RowMap rm{lead, row_pixels, zc ? zero_pixel : nullptr, zc * es / 16};
+    bn_bwd_apply_kernel<true, true><<<nb, NT, 0, s>>>(dact, x, dx, dtype, P, C, gamma, mean, invstd, dgamma, dbeta,
+                                                      dbias ? (float*)partial : nullptr, scale, shift, rm, w,
+                                                      make_fastdiv((uint32_t)w));
+  } else {
+    bn_bwd_apply_kernel<true><<<nb, NT, 0, s>>>(dact, x, dx, dtype, P, C, gamma, mean, invstd, dgamma, dbeta,
+                                                dbias ? (float*)partial : nullptr, scale, shift);
+  }
   MIA_LAUNCH_CHECK("bn_relu_bwd_apply");
   if (dbias) {
     cp_final2_kernel<<<(unsigned)C, 256, 0, s>>>((const float*)partial, nb, C, /*q0 = sum dx*/ dbias, nullptr);
     MIA_LAUNCH_CHECK("channel_partial_sum");
   }
   return 0;
+}
+
+extern "C" int mia_bn_relu_bwd_apply(const void* dact, const void* x, void* dx, int32_t dtype, int64_t P, int32_t C,
+                                     const float* gamma, const float* scale, const float* shift, const float* mean,
+                                     const float* invstd, const float* dgamma, const float* dbeta, float* dbias,
+                                     void* partial, mia_stream_t stream) {
+  return mia_bn_relu_bwd_apply_rows(dact, x, dx, dtype, P, C, 1, 0, 1, nullptr, 0, gamma, scale, shift, mean, invstd,
+                                    dgamma, dbeta, dbias, partial, stream);
 }
 
 extern "C" int mia_colsum(const void* x, int32_t dtype, int64_t P, int32_t C, int64_t ld, float* out, void* partial,

@@ -8,24 +8,13 @@
 #include <cstdlib>
 
 #include "../../include/miaudio_pool.h"
+#include "../../include/miaudio_rowmap.h"
 #include "bn_math.h"
 #include "channel_partials.h"
 
 namespace {
 
 constexpr int NT = CP_NT;
-
-// n / d for 0 <= n < 2^31 without an integer division (Granlund-Montgomery: one mul_hi, add, shift)
-struct FastDiv {
-  uint32_t d, m, l;
-};
-static FastDiv make_fastdiv(uint32_t d) {
-  uint32_t l = 0;
-  while ((1u << l) < d) ++l;
-  const uint32_t m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - d)) / d + 1);
-  return FastDiv{d, m, l};
-}
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) { return (__umulhi(n, f.m) + n) >> f.l; }
 
 __device__ __forceinline__ int64_t out_index(int layout, int b, int oy, int ox, int c, int OH, int OW, int C) {
   if (layout == 0) return (((int64_t)b * OH + oy) * OW + ox) * C + c;
@@ -731,7 +720,10 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_oct_kernel(const void* _
 // thread-iteration, all loads issued before any use.  EnvNet block 0 (B = 256, 50 x 846 x 32, (5, 3)):
 // 0.447 ms per pixel -> 0.345 ms per run (4.25 TB/s on x + dx + gm); folding the five per-channel
 // constants into three (occupancy 4 -> 5) measured no faster.
-template <int KW, int RU, int GDT>
+// RM: dx through a row map (RowMap, common.h): pixel ix of row b*H + iy is stored at pixel lead + (b*H + iy) * rowpx +
+// ix.  The thread that owns a row's last run also zeroes that row's pixels W .. rowpx - 1, the one that owns run 0
+// of row 0 the lead pixels, block 0 the zero pixel -- same grid, same runs, same sums.
+template <int KW, int RU, int GDT, bool RM = false>
 __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const void* __restrict__ gm,
                                                                    const uint8_t* __restrict__ argmax,
                                                                    const bf16* __restrict__ x, int n, int H, int W,
@@ -741,11 +733,15 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const void* _
                                                                    const float* __restrict__ invstd,
                                                                    const float* __restrict__ dgamma,
                                                                    const float* __restrict__ dbeta, bf16* dx,
-                                                                   float* __restrict__ partial) {
+                                                                   float* __restrict__ partial, RowMap rm = RowMap{}) {
   const int OH = H / kh, OW = W / KW, G = C / 8, NR = (W + KW - 1) / KW;
   const int t = threadIdx.x;
   const int cg = t % G;
   const int P = n * H * W;
+  if constexpr (RM) {
+    if (rm.zp && blockIdx.x == 0)
+      for (int i = t; i < rm.zc16; i += NT) reinterpret_cast<uint4*>(rm.zp)[i] = uint4{0u, 0u, 0u, 0u};
+  }
   BnApply8 bn;
   bn.load(cg, gamma, mean, invstd, dgamma, dbeta, 1.f / (float)P);
   float s1[8] = {0};
@@ -756,7 +752,9 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const void* _
     uint2 am[RU];
     Raw8<GDT> gr[RU];
     int64_t xoff[RU];
+    int64_t doff[RU];  // RM: where the run's first pixel goes in dx
     int pos0[RU], ix0[RU];
+    bool first[RU];
 #pragma unroll
     for (int v = 0; v < RU; ++v) {
       const int u = min(u0 + v * stride, units - 1);
@@ -773,6 +771,13 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const void* _
       am[v] = *reinterpret_cast<const uint2*>(argmax + coff);
       gr[v].load(gm, coff);
       xoff[v] = ((int64_t)rowi * W + ix0[v]) * C + cg * 8;
+      if constexpr (RM) {
+        doff[v] = (rm.lead + (int64_t)rowi * rm.rowpx + ix0[v]) * C + cg * 8;
+        first[v] = rest == 0;
+      } else {
+        doff[v] = xoff[v];
+        first[v] = false;
+      }
 #pragma unroll
       for (int j = 0; j < KW; ++j) {
         const int64_t o = ix0[v] + j < W ? xoff[v] + (int64_t)j * C : xoff[v];
@@ -802,7 +807,15 @@ __global__ __launch_bounds__(NT) void pool_bn_bwd_apply_run_kernel(const void* _
           }
           o4[q] = pk_bf16(g[0], g[1]);
         }
-        *reinterpret_cast<uint4*>(dx + xoff[v] + (int64_t)j * C) = uint4{o4[0], o4[1], o4[2], o4[3]};
+        *reinterpret_cast<uint4*>(dx + doff[v] + (int64_t)j * C) = uint4{o4[0], o4[1], o4[2], o4[3]};
+      }
+      if constexpr (RM) {
+        if (ix0[v] + KW >= W)  // the row's last run: its zero pixels W .. rowpx - 1
+          for (int px = W - ix0[v]; px < rm.rowpx - ix0[v]; ++px)
+            *reinterpret_cast<uint4*>(dx + doff[v] + (int64_t)px * C) = uint4{0u, 0u, 0u, 0u};
+        if (first[v])
+          for (int px = 0; px < rm.lead; ++px)
+            *reinterpret_cast<uint4*>(dx + (int64_t)px * C + cg * 8) = uint4{0u, 0u, 0u, 0u};
       }
     }
   }
@@ -1000,8 +1013,9 @@ extern "C" int mia_pool_bwd_bn_relu_reduce(const void* dout, int32_t out_layout,
   return 0;
 }
 
-// MIA_POOL_GRID=n, read at call time: at most n blocks for mia_pool_bwd_gather's main kernel, whichever form runs
-// (it only lowers the grid; the tests use it to make a thread walk many cells at small shapes)
+// MIA_POOL_GRID=n, read at call time: at most n blocks for mia_pool_bwd_gather's main kernel, whichever form runs,
+// and for the run form of mia_pool_bn_relu_bwd_apply (it only lowers the grid; the tests use it to make a thread
+// walk many cells at small shapes)
 static int pool_grid_cap(int nb) {
   const char* e = getenv("MIA_POOL_GRID");
   const int cap = e ? atoi(e) : 0;
@@ -1075,7 +1089,8 @@ template <int GDT>
 static int pool_bn_bwd_apply_launch(const void* gm, const uint8_t* argmax, const void* x, int32_t dtype, int32_t n,
                                     int32_t h, int32_t w, int32_t c, int32_t kh, int32_t kw, const float* gamma,
                                     const float* mean, const float* invstd, const float* dgamma, const float* dbeta,
-                                    void* dx, float* dbias, void* partial, hipStream_t s) {
+                                    void* dx, float* dbias, void* partial, hipStream_t s, const RowMap& rm) {
+  const bool mapped = rm.lead != 0 || rm.rowpx != w || rm.zp;
   const int rslots = NT / (c / 8);
   const int64_t P = (int64_t)n * h * w;
   const int64_t units = (int64_t)n * h * ((w + 7) / 8) * (c / 8);
@@ -1088,7 +1103,7 @@ static int pool_bn_bwd_apply_launch(const void* gm, const uint8_t* argmax, const
     }
     return 0;
   };
-  if (kw % 8 == 0 && dtype == MIA_BF16 && units < (1ll << 31) &&
+  if (!mapped && kw % 8 == 0 && dtype == MIA_BF16 && units < (1ll << 31) &&
       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(units, NT), CP_MAXBLK));
     pool_bn_bwd_apply_oct_kernel<GDT><<<nb, NT, 0, s>>>(gm, argmax, reinterpret_cast<const bf16*>(x), n, h, w, c, kh, kw,
@@ -1102,11 +1117,24 @@ static int pool_bn_bwd_apply_launch(const void* gm, const uint8_t* argmax, const
   if (kw >= 2 && kw <= 4 && dtype == MIA_BF16 && runs < (1ll << 31) && !per_pixel &&
       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
     constexpr int RU = PB_RUNS;
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(runs, (int64_t)NT * RU), PB_NB));
+    const int nb = pool_grid_cap((int)std::max<int64_t>(1, std::min<int64_t>(cdiv(runs, (int64_t)NT * RU), PB_NB)));
     const FastDiv dNR = make_fastdiv((int)cdiv(w, kw)), dH = make_fastdiv(h), dG = make_fastdiv(c / 8);
     float* part = dbias ? (float*)partial : nullptr;
     const bf16* xb = reinterpret_cast<const bf16*>(x);
     bf16* dxb = reinterpret_cast<bf16*>(dx);
+    if (mapped) {
+      MIA_CHECK_ARG(((int64_t)rm.lead + (int64_t)n * h * rm.rowpx) * c < (1ll << 40), "pool_bn_bwd_apply: row map size");
+      if (kw == 2)
+        pool_bn_bwd_apply_run_kernel<2, RU, GDT, true><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma,
+                                                                         mean, invstd, dgamma, dbeta, dxb, part, rm);
+      else if (kw == 3)
+        pool_bn_bwd_apply_run_kernel<3, RU, GDT, true><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma,
+                                                                         mean, invstd, dgamma, dbeta, dxb, part, rm);
+      else
+        pool_bn_bwd_apply_run_kernel<4, RU, GDT, true><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma,
+                                                                         mean, invstd, dgamma, dbeta, dxb, part, rm);
+      return finish("pool_bn_bwd_apply_run", nb);
+    }
     if (kw == 2)
       pool_bn_bwd_apply_run_kernel<2, RU, GDT><<<nb, NT, 0, s>>>(gm, argmax, xb, n, h, w, c, kh, dNR, dH, dG, gamma,
                                                                  mean, invstd, dgamma, dbeta, dxb, part);
@@ -1118,6 +1146,8 @@ static int pool_bn_bwd_apply_launch(const void* gm, const uint8_t* argmax, const
                                                                  mean, invstd, dgamma, dbeta, dxb, part);
     return finish("pool_bn_bwd_apply_run", nb);
   }
+  // the row map is served by the run form alone (bf16 activations, kw = 2..4, any kh, 16-byte aligned x and dx)
+  MIA_CHECK_ARG(!mapped, "pool_bn_bwd_apply: a row map needs the run form (bf16, kw 2..4, 16-byte aligned x / dx)");
   const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(P, (int64_t)rslots * 8), CP_MAXBLK));
   pool_bn_bwd_apply_kernel<GDT><<<nb, NT, 0, s>>>(gm, argmax, x, dtype, n, h, w, c, kh, kw, make_fastdiv(w),
                                                   make_fastdiv(h), make_fastdiv(kw), make_fastdiv(kh), gamma, mean,
@@ -1125,11 +1155,15 @@ static int pool_bn_bwd_apply_launch(const void* gm, const uint8_t* argmax, const
   return finish("pool_bn_bwd_apply", nb);
 }
 
-extern "C" int mia_pool_bn_relu_bwd_apply_ex(const void* gm, int32_t gm_dtype, const uint8_t* argmax, const void* x,
-                                             int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh,
-                                             int32_t kw, const float* gamma, const float* mean, const float* invstd,
-                                             const float* dgamma, const float* dbeta, void* dx, float* dbias,
-                                             void* partial, mia_stream_t stream) {
+extern "C" int mia_pool_bn_relu_bwd_apply_rows(const void* gm, int32_t gm_dtype, const uint8_t* argmax, const void* x,
+                                               int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh,
+                                               int32_t kw, const float* gamma, const float* mean, const float* invstd,
+                                               const float* dgamma, const float* dbeta, void* dx, int32_t lead,
+                                               int32_t row_pixels, void* zero_pixel, int32_t zc, float* dbias,
+                                               void* partial, mia_stream_t stream) {
+  MIA_CHECK_ARG(lead >= 0 && row_pixels >= w && zc >= 0 && zc % 8 == 0 && (zc == 0 || zero_pixel),
+                "pool_bn_bwd_apply: bad row map (lead %d, row_pixels %d, w %d, zc %d)", lead, row_pixels, w, zc);
+  MIA_CHECK_ARG(!zero_pixel || aligned16(zero_pixel), "pool_bn_bwd_apply: zero_pixel alignment");
   MIA_CHECK_ARG(gm && argmax && x && mean && invstd && dgamma && dbeta && dx, "pool_bn_bwd_apply: null pointer");
   MIA_CHECK_ARG(!dbias || partial, "pool_bn_bwd_apply: dbias needs the partial workspace");
   MIA_CHECK_ARG(c % 8 == 0 && c >= 8 && (NT % (c / 8)) == 0, "pool_bn_bwd_apply: channels");
@@ -1139,11 +1173,21 @@ extern "C" int mia_pool_bn_relu_bwd_apply_ex(const void* gm, int32_t gm_dtype, c
   // a cell's eight channels are read as 16-B vectors (one of bf16, two of f32)
   MIA_CHECK_ARG((reinterpret_cast<uintptr_t>(gm) & 15) == 0, "pool_bn_bwd_apply: gm alignment");
   hipStream_t s = as_stream(stream);
+  const RowMap rm{lead, row_pixels, zc ? zero_pixel : nullptr, zc / 8};
   if (gm_dtype == MIA_BF16)
     return pool_bn_bwd_apply_launch<MIA_BF16>(gm, argmax, x, dtype, n, h, w, c, kh, kw, gamma, mean, invstd, dgamma,
-                                              dbeta, dx, dbias, partial, s);
+                                              dbeta, dx, dbias, partial, s, rm);
   return pool_bn_bwd_apply_launch<MIA_F32>(gm, argmax, x, dtype, n, h, w, c, kh, kw, gamma, mean, invstd, dgamma, dbeta,
-                                           dx, dbias, partial, s);
+                                           dx, dbias, partial, s, rm);
+}
+
+extern "C" int mia_pool_bn_relu_bwd_apply_ex(const void* gm, int32_t gm_dtype, const uint8_t* argmax, const void* x,
+                                             int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, int32_t kh,
+                                             int32_t kw, const float* gamma, const float* mean, const float* invstd,
+                                             const float* dgamma, const float* dbeta, void* dx, float* dbias,
+                                             void* partial, mia_stream_t stream) {
+  return mia_pool_bn_relu_bwd_apply_rows(gm, gm_dtype, argmax, x, dtype, n, h, w, c, kh, kw, gamma, mean, invstd, dgamma,
+                                         dbeta, dx, 0, w, nullptr, 0, dbias, partial, stream);
 }
 
 extern "C" int mia_pool_bn_relu_bwd_apply(const float* gm, const uint8_t* argmax, const void* x, int32_t dtype,

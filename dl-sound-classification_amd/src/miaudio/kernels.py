@@ -364,10 +364,20 @@ def bn_bwd_apply(dz, x, dx, P, C, gamma, bn: BNState, dgamma, dbeta, dbias=None)
                                  dbeta.data_ptr(), L.ptr(dbias), ws.data_ptr(), _s()), "mia_bn_bwd_apply")
 
 
-def bn_relu_bwd_apply(dact, x, dx, P, C, gamma, bn: BNState, dgamma, dbeta, dbias=None):
-    """dx = BN backward of relu(bn(x)) with the ReLU mask recomputed from x (one pass)."""
+def bn_relu_bwd_apply(dact, x, dx, P, C, gamma, bn: BNState, dgamma, dbeta, dbias=None, rowmap=None):
+    """dx = BN backward of relu(bn(x)) with the ReLU mask recomputed from x (one pass).  ``rowmap`` = (w, lead,
+    row_pixels, zero_pixel): dx through a row map (include/miaudio_rowmap.h; zero_pixel a tensor or None)."""
     lib = L.load()
     ws = workspace(lib.mia_bn_partial_bytes(P, C), x.device, "bn")
+    if rowmap is not None:
+        w, lead, rowpx, zp = rowmap
+        assert dx.numel() == (lead + P // w * rowpx) * C
+        L.check(lib.mia_bn_relu_bwd_apply_rows(dact.data_ptr(), x.data_ptr(), dx.data_ptr(), L.dtype_code(x), P, C, w,
+                                               lead, rowpx, L.ptr(zp), 0 if zp is None else zp.numel(), L.ptr(gamma),
+                                               bn.scale.data_ptr(), bn.shift.data_ptr(), bn.mean.data_ptr(),
+                                               bn.invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                               L.ptr(dbias), ws.data_ptr(), _s()), "mia_bn_relu_bwd_apply_rows")
+        return
     L.check(lib.mia_bn_relu_bwd_apply(dact.data_ptr(), x.data_ptr(), dx.data_ptr(), L.dtype_code(x), P, C,
                                       L.ptr(gamma), bn.scale.data_ptr(), bn.shift.data_ptr(), bn.mean.data_ptr(),
                                       bn.invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), L.ptr(dbias),
@@ -397,10 +407,22 @@ def pool_bwd_gather(dout, out_layout, argmax, x, n, h, w, c, kh, kw, bn: BNState
     return gm, g[0], g[1]
 
 
-def pool_bn_relu_bwd_apply(gm, argmax, x, n, h, w, c, kh, kw, gamma, bn: BNState, dgamma, dbeta, dx, dbias=None):
-    """Dense half: BN backward of the pooled layer, g taken from gm (f32 or bf16) at the argmax (one pass x -> dx)."""
+def pool_bn_relu_bwd_apply(gm, argmax, x, n, h, w, c, kh, kw, gamma, bn: BNState, dgamma, dbeta, dx, dbias=None,
+                           rowmap=None):
+    """Dense half: BN backward of the pooled layer, g taken from gm (f32 or bf16) at the argmax (one pass x -> dx).
+    ``rowmap`` = (lead, row_pixels, zero_pixel): dx through a row map (include/miaudio_rowmap.h)."""
     lib = L.load()
     ws = workspace(lib.mia_bn_partial_bytes(n * h * w, c), x.device, "bn")
+    if rowmap is not None:
+        lead, rowpx, zp = rowmap
+        assert dx.numel() == (lead + n * h * rowpx) * c
+        L.check(lib.mia_pool_bn_relu_bwd_apply_rows(gm.data_ptr(), L.dtype_code(gm), argmax.data_ptr(), x.data_ptr(),
+                                                    L.dtype_code(x), n, h, w, c, kh, kw, L.ptr(gamma),
+                                                    bn.mean.data_ptr(), bn.invstd.data_ptr(), dgamma.data_ptr(),
+                                                    dbeta.data_ptr(), dx.data_ptr(), lead, rowpx, L.ptr(zp),
+                                                    0 if zp is None else zp.numel(), L.ptr(dbias), ws.data_ptr(),
+                                                    _s()), "mia_pool_bn_relu_bwd_apply_rows")
+        return
     L.check(lib.mia_pool_bn_relu_bwd_apply_ex(gm.data_ptr(), L.dtype_code(gm), argmax.data_ptr(), x.data_ptr(),
                                               L.dtype_code(x), n, h, w, c, kh, kw, L.ptr(gamma), bn.mean.data_ptr(),
                                               bn.invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
@@ -687,30 +709,59 @@ W2_SHIFT = os.environ.get("MIA_W2_SHIFT", "0") == "1"  # A/B switch: the interle
 W2_DROPCOPY = os.environ.get("MIA_W2_DROPCOPY", "0") == "1"  # A/B switch: full-grid forward output + column drop
 
 
+def w2_padcopy() -> bool:
+    """A/B switch, read at call time: MIA_W2_PADCOPY=1 lays the gradient of a (1, 2) conv on the input grid with
+    the copy pass (mia_pad_w2) instead of having its producer store it there (w2_grad_buffer)."""
+    return os.environ.get("MIA_W2_PADCOPY", "0") == "1"
+
+
+def w2_grad_buffer(rows: int, w: int, cout: int, a: torch.Tensor, cin: int):
+    """For the producer of a (1, 2) conv's output gradient: (G, rowmap) with G the ((rows * w + 1) * cout,) bf16
+    buffer of trunk_bwd_w2's laid-out form (the "w2shift" workspace) and rowmap = (lead, row_pixels, zero_pixel)
+    for pool_bn_relu_bwd_apply / bn_relu_bwd_apply (after the source width): one zero pixel, then every
+    (w - 1)-pixel gradient row followed by one zero column; zero_pixel is the pad pixel of the forward input a.
+    None under MIA_W2_SHIFT=1 or MIA_W2_PADCOPY=1, whose forms take the dense gradient."""
+    if W2_SHIFT or w2_padcopy():
+        return None
+    P = rows * w
+    assert a.untyped_storage().nbytes() - a.storage_offset() * 2 >= (P + 1) * cin * 2, "a needs a pad pixel"
+    G = workspace((P + 1) * cout * 2, a.device, "w2shift")[: (P + 1) * cout * 2].view(torch.bfloat16)
+    pad = torch.empty(0, dtype=a.dtype, device=a.device).set_(a.untyped_storage(), a.storage_offset() + P * cin, (cin,))
+    return G, (1, w, pad)
+
+
 def trunk_bwd_w2(dy: torch.Tensor, a: torch.Tensor, rows: int, w: int, cout: int, cin: int, wpk: torch.Tensor,
-                 dw: torch.Tensor, dx: torch.Tensor, tag: str = "", wflip: torch.Tensor | None = None):
+                 dw: torch.Tensor, dx: torch.Tensor, tag: str = "", wflip: torch.Tensor | None = None,
+                 G: torch.Tensor | None = None):
     """Backward of a (1, 2) conv, stride 1 (EnvNet trunk blocks 3-4).  One pass lays dy on the input grid
     (G = [zero pixel] + dy with a zero last column per row, mia_pad_w2; it also zeroes a's pad pixel), then two
     dense GEMMs through overlapping views of G and a (rows of 2 pixels at a 1-pixel stride):
     dw (cout, 2*cin) OHWI f32 = G[1:]^T [a[q], a[q+1]], and dx (rows*w, cin) bf16 = [G[q], G[q+1]] Wflip with
     Wflip = the mode-1 pack (cin, 2*cout), [ci][kx'][co] = W[co][ci][0][1-kx'] -- half the bytes of the
     interleaved shifted copy Ashift[q][co*2+kx] = dy[q-kx][co] of the previous form (MIA_W2_SHIFT=1, which
-    uses wpk (cout, 2*cin) read as the (2*cout, cin) K-major matrix).  a must carry one pad pixel."""
-    assert dy.dtype == torch.bfloat16 and a.dtype == torch.bfloat16 and dw.dtype == torch.float32
-    assert dy.numel() == rows * (w - 1) * cout and a.numel() == rows * w * cin and dw.numel() == cout * 2 * cin
+    uses wpk (cout, 2*cin) read as the (2*cout, cin) K-major matrix).  a must carry one pad pixel.
+    ``G``: the gradient already laid out by its producer (w2_grad_buffer), a's pad pixel zeroed: dy is None then
+    and the copy pass is skipped."""
+    assert a.dtype == torch.bfloat16 and dw.dtype == torch.float32
+    assert a.numel() == rows * w * cin and dw.numel() == cout * 2 * cin
+    if G is None:
+        assert dy.dtype == torch.bfloat16 and dy.numel() == rows * (w - 1) * cout
     assert dx.numel() == rows * w * cin and dx.dtype == torch.bfloat16 and wpk.numel() == cout * 2 * cin
     P = rows * w
     if not W2_SHIFT and wflip is not None:
         assert a.untyped_storage().nbytes() - a.storage_offset() * 2 >= (P + 1) * cin * 2, "a needs a pad pixel"
-        G = workspace((P + 1) * cout * 2, dy.device, "w2shift")[: (P + 1) * cout * 2].view(torch.bfloat16)
-        L.check(L.load().mia_pad_w2(dy.data_ptr(), rows, w, cout, G.data_ptr(), a.data_ptr() + P * cin * 2, cin, _s()),
-                "mia_pad_w2")
+        if G is None:
+            G = workspace((P + 1) * cout * 2, dy.device, "w2shift")[: (P + 1) * cout * 2].view(torch.bfloat16)
+            L.check(L.load().mia_pad_w2(dy.data_ptr(), rows, w, cout, G.data_ptr(), a.data_ptr() + P * cin * 2, cin,
+                                        _s()), "mia_pad_w2")
+        assert G.dtype == torch.bfloat16 and G.numel() == (P + 1) * cout
         G1 = G[cout:]
         gemm(dense(G1, L.RC, P, cout), dense(a, L.RC, P, 2 * cin, ld=cin), epilogue(dw, 2 * cin), cout, 2 * cin, P,
              L.BF16, tag=f"{tag}.wgrad" if tag else None)
         gemm(dense(G, L.KC, P, 2 * cout, ld=cout), dense(wflip, L.KC, cin, 2 * cout), epilogue(dx, cin), P, cin,
              2 * cout, L.BF16, tag=f"{tag}.dgrad" if tag else None)
         return
+    assert G is None, "a laid-out G needs the pad form (wflip, not MIA_W2_SHIFT)"
     ash = workspace(P * 2 * cout * 2, dy.device, "w2shift")[: P * 2 * cout * 2].view(torch.bfloat16)
     L.check(L.load().mia_shift_pad_w2(dy.data_ptr(), rows, w, cout, ash.data_ptr(), _s()), "mia_shift_pad_w2")
     gemm(dense(ash, L.RC, P, 2 * cout), dense(a, L.RC, P, cin), epilogue(dw, cin), 2 * cout, cin, P, L.BF16,

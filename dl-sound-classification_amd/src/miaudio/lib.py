@@ -107,6 +107,11 @@ SIGNATURES = {
                                          i32, vp, vp, vp, vp]),
     "mia_pool_bn_relu_bwd_apply_ex": (C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp,
                                                 vp, vp, vp, vp]),
+    # include/miaudio_rowmap.h: the two producers of a (1, 2)-conv backward's gradient, storing through a row map
+    "mia_pool_bn_relu_bwd_apply_rows": (C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp,
+                                                  vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "mia_bn_relu_bwd_apply_rows": (C.c_int, [vp, vp, vp, i32, i64, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp,
+                                             vp, vp, vp, vp, vp]),
     "mia_pool_fwd": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp]),
     "mia_pool_bwd_bn_relu_reduce": (C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp,
                                               vp, vp, vp, vp, vp, vp]),

@@ -389,10 +389,18 @@ class EnvNetFunction(torch.autograd.Function):
             gm, dgb, dbb = K.pool_bwd_gather(dpool, lay, ts["am"], ts["yb"], B, hb, wb, cout2, ph, pw, ts["bnb"],
                                              win=ts["win"])
             grads[pa + 6], grads[pa + 7] = dgb, dbb
-            dyb = torch.empty(Pb, cout2, dtype=tdt, device=dev)
             dbias_b = torch.empty(cout2, dtype=torch.float32, device=dev)
-            K.pool_bn_relu_bwd_apply(gm, ts["am"], ts["yb"], B, hb, wb, cout2, ph, pw, bns[3 + 2 * blk].weight,
-                                     ts["bnb"], dgb, dbb, dyb, dbias_b)
+            # (1, 2) conv: its producer stores the gradient on the conv's input grid (K.w2_grad_buffer), unless
+            # MIA_W2_PADCOPY / MIA_W2_SHIFT ask for the dense gradient and a copy pass
+            Gb = K.w2_grad_buffer(B * ha, wa, cout2, ts["act"], cin2) if ts["act"] is not None else None
+            if Gb is None:
+                dyb = torch.empty(Pb, cout2, dtype=tdt, device=dev)
+                K.pool_bn_relu_bwd_apply(gm, ts["am"], ts["yb"], B, hb, wb, cout2, ph, pw, bns[3 + 2 * blk].weight,
+                                         ts["bnb"], dgb, dbb, dyb, dbias_b)
+            else:
+                dyb = None
+                K.pool_bn_relu_bwd_apply(gm, ts["am"], ts["yb"], B, hb, wb, cout2, ph, pw, bns[3 + 2 * blk].weight,
+                                         ts["bnb"], dgb, dbb, Gb[0], dbias_b, rowmap=Gb[1])
             grads[pa + 5] = dbias_b
             # wgrad b: dW[co][(ky,kx,ci)] = sum_pix dyb[pix][co] * relu(bn_a(ya))[pix + tap][ci]
             Kb = kh2 * kw2 * cin2
@@ -403,7 +411,7 @@ class EnvNetFunction(torch.autograd.Function):
             if ts["act"] is not None:
                 # (1, 2) conv: shifted dY once, then wgrad and dgrad as two dense GEMMs
                 K.trunk_bwd_w2(dyb, ts["act"], B * ha, wa, cout2, cin2, wpk[pa + 4], dWb, da, wflip=wbk[(pa + 4, 1)],
-                               tag=f"t{blk}b")
+                               tag=f"t{blk}b", G=None if Gb is None else Gb[0])
             else:
                 K.gemm(K.dense(dyb, L.RC, Pb, cout2),
                        K.conv(ts["ya"], L.RC, B, ha, wa, cin2, hb, wb, kh2, kw2, pre=L.PRE_AFFINE_RELU,
@@ -433,10 +441,16 @@ class EnvNetFunction(torch.autograd.Function):
             dWa = torch.empty(cout, Ka, dtype=torch.float32, device=dev)
             dense_w2 = ts["act"] is not None
             c3w = cin == 1 and cd == L.BF16 and kh == 8 and kw == 8 and cout == 32 and W % 4 == 0
+            Ga = K.w2_grad_buffer(B * H, W, cout, ts["inp"], cin) if dense_w2 else None
             if c3w and not C3_BNSEP:
                 # conv3: the ReLU+BN backward applied while the weight-gradient kernel stages dY (in place)
                 K.conv3_wgrad_bn(ts["inp"], da, ts["ya"], da, dWa, dbias_a, B, H, W, bns[2 + 2 * blk].weight,
                                  ts["bna"], dga, dba, tag=f"t{blk}a.wgrad")
+            elif Ga is not None:
+                # the (1, 2) conv a: dya straight onto its input grid (the buffer conv b's gradient has left)
+                K.bn_relu_bwd_apply(da, ts["ya"], Ga[0], Pa, cout, bns[2 + 2 * blk].weight, ts["bna"], dga, dba,
+                                    dbias_a, rowmap=(wa, *Ga[1]))
+                dya = None
             else:
                 K.bn_relu_bwd_apply(da, ts["ya"], da, Pa, cout, bns[2 + 2 * blk].weight, ts["bna"], dga, dba,
                                     dbias_a)
@@ -446,7 +460,7 @@ class EnvNetFunction(torch.autograd.Function):
             elif dense_w2:
                 dinp = torch.empty(B * H * W, cin, dtype=tdt, device=dev)
                 K.trunk_bwd_w2(dya, ts["inp"].reshape(B * H * W, cin), B * H, W, cout, cin, wpk[pa],
-                               dWa, dinp, tag=f"t{blk}a", wflip=wbk[(pa, 1)])
+                               dWa, dinp, tag=f"t{blk}a", wflip=wbk[(pa, 1)], G=None if Ga is None else Ga[0])
             elif c3w:
                 # conv3 weight gradient: wave-persistent, dY read once (csrc/conv3w.hip)
                 K.conv3_wgrad(ts["inp"], dya, dWa, B, H, W, tag=f"t{blk}a.wgrad")
